@@ -31,6 +31,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -244,6 +245,58 @@ def live_traffic(args, kernel_name):
                     f"+ write {1024 * per['WRITE_SIZE'][0] / 1e6:.1f} MB per launch"), extra
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_LOGIT_ROWS = 96                # sampled (sequence, position) rows of the logits, besides every sequence's last position
+DUMP_KV_PER_LAYER = 16384           # sampled elements of each layer's K and of its V
+
+
+def _sample(n_total, n, tag):
+    """A fixed, sorted sample of min(n, n_total) indices of range(n_total): the same for the same shapes on every run."""
+    rng = np.random.default_rng([20240607, n_total, n, sum(map(ord, tag))])
+    return np.sort(rng.choice(n_total, size=min(n, n_total), replace=False))
+
+
+def _take(pieces, b, r, tail=()):
+    """Entries [b[i], r[i]] of the batch-wise concatenation of `pieces` ((b0, b1, tensor [b1 - b0, ...]) each), every piece viewed
+    as [b1 - b0, -1, *tail]: fp32 numpy [len(b), *tail]."""
+    out = np.empty((len(b), *tail), dtype=np.float32)
+    for b0, b1, t in pieces:
+        m = (b >= b0) & (b < b1)
+        if m.any():
+            bi, ri = (torch.from_numpy(x[m]).to(t.device) for x in (b - b0, r))
+            out[m] = t.reshape(b1 - b0, -1, *tail)[bi, ri].float().cpu().numpy()
+    return out
+
+
+def prefill_outputs(outs, cuts, S):
+    """What a caller of the prefill step receives (CausalLMOutputWithPast per sub-batch: fp32 logits [b, S, V] and the filled
+    KV cache, L x (K, V) [b, heads, S, 128]), reduced to a fixed sample that stays under DUMP_LIMIT_BYTES: every sequence's
+    last-position logits (what decoding continues from), DUMP_LOGIT_ROWS whole logit rows at sampled (sequence, position)
+    pairs, and DUMP_KV_PER_LAYER sampled elements of every layer's K and V (the same positions in each layer)."""
+    Bp, V = cuts[-1], outs[0].logits.shape[-1]
+    res = {"logits_last": np.concatenate([o.logits[:, -1].float().cpu().numpy() for o in outs])}
+    rows = _sample(Bp * S, DUMP_LOGIT_ROWS, "logits_rows")
+    res["logits_rows"] = _take([(cuts[i], cuts[i + 1], o.logits) for i, o in enumerate(outs)], rows // S, rows % S, (V,))
+    c0 = outs[0].past_key_values
+    inner = c0.k[0].shape[1] * S * c0.k[0].shape[3]
+    idx = _sample(Bp * inner, DUMP_KV_PER_LAYER, "kv")
+    for name in ("k", "v"):
+        res[f"kv_{name}"] = np.stack([_take([(cuts[i], cuts[i + 1], getattr(o.past_key_values, name)[layer][:, :, :S])
+                                             for i, o in enumerate(outs)], idx // inner, idx % inner)
+                                      for layer in range(len(c0.k))])
+    return res
+
+
+def dump_outputs(dirname, arrays):
+    """DIR/<name>.npy for each array (float32 / float64 only), DUMP_LIMIT_BYTES in all."""
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}"
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 ALSO = {
     # key in the JSON line: (child arguments, BASELINE.json configuration it is)
     "c2": (["--config", "c2", "--steps", "10", "--warmup", "3"], "configs[1]"),
@@ -332,7 +385,13 @@ def main():
                          "line under `also` (N = 1 only): comma list of c2 (configs[1]), c4 (configs[3]'s per-GPU shape at N = 1), "
                          "decode (configs[4]: 13B, 256 tokens, hipGraph step), c3_fp16 (the headline workload on the fp16 library); "
                          "'auto' = all four for the default c3 run, 'none' = off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, tokens float64; rank 0's outputs; "
+                         "a fixed sample of the logits and KV cache, at most 64 MB): same arguments, same inputs, so two builds compare "
+                         "output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     os.environ["VALLEY_PACK_WEIGHTS"] = str(args.pack_weights)      # read by the engines when they load their weights
 
     rank = int(os.environ.get("RANK", "0"))
@@ -434,6 +493,9 @@ def main():
         torch.cuda.synchronize()
         wall = time.perf_counter() - t0
         assert len(toks) == R
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"tokens": np.asarray([toks[r] for r in range(R)], dtype=np.float64),
+                                             "logits": cb.sess.logits[:R, :mm.llama.V].float().cpu().numpy()})
         ms_step = e0.elapsed_time(e1) / n_new
         wbytes = 2.0 * (L * (4 * H * H + 3 * H * I) + H * mm.llama.Vpad)
         ctx_mid = S + args.warmup + n_new / 2
@@ -467,10 +529,13 @@ def main():
         t0 = time.perf_counter()
         e0.record()
         for _ in range(n_new):
-            sess.step()
+            tok = sess.step()
         e1.record()
         torch.cuda.synchronize()
         wall = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"tokens": tok.double().cpu().numpy(),
+                                             "logits": sess.logits[:, :mm.llama.V].float().cpu().numpy()})
         ms_tok = e0.elapsed_time(e1) / n_new
         wbytes = 2.0 * (L * (4 * H * H + 3 * H * I) + H * mm.llama.Vpad)
         ctx_mid = S + args.warmup + n_new / 2
@@ -539,15 +604,14 @@ def main():
                              visual_tokens=visual[cuts_p[i] * nv:cuts_p[i + 1] * nv],
                              frames_per_clip=Ts_all[cuts_p[i]:cuts_p[i + 1]])
             outs = fork_join(pre)
-            out = outs[-1]
         else:
             cache.seq_len = 0
-            out = model(input_ids=input_ids, past_key_values=cache, use_cache=True, visual_tokens=visual,
-                        frames_per_clip=Ts_all[:Bp])
+            outs = [model(input_ids=input_ids, past_key_values=cache, use_cache=True, visual_tokens=visual,
+                          frames_per_clip=Ts_all[:Bp])]
         if record:
             e2.record()
             stage_events.append((e0, e1, e2))
-        return out
+        return outs                                                      # one output per sub-batch (cuts_p)
 
     # untimed: the online GEMM tuner (ops.gemm) tries its candidate kernels in place, one per call and shape;
     # run steps until every shape on the path is decided (all ranks take the same number of passes)
@@ -577,13 +641,17 @@ def main():
     t0 = time.perf_counter()
     for it in range(args.steps):
         ops.set_recorder(rec if (rec is not None and it % EVENT_STRIDE == 0) else None)
-        out = step(True)
+        outs = step(True)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     ops.set_recorder(None)
+    out = outs[-1]
     assert torch.isfinite(out.logits[:, -1]).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, prefill_outputs(outs, cuts_p, S))
+    del outs
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
