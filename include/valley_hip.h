@@ -30,11 +30,12 @@
 extern "C" {
 #endif
 
-#define VLY_ABI_VERSION 7   /* 2: + the fp32 "precise" entry points (vly_*_f32); 3: + vly_storage_dtype; 4: + vly_gemv_rmsnorm_bf16,
+#define VLY_ABI_VERSION 8   /* 2: + the fp32 "precise" entry points (vly_*_f32); 3: + vly_storage_dtype; 4: + vly_gemv_rmsnorm_bf16,
                                vly_decode_attention_split, vly_gemv_attnmerge_bf16; 5: + vly_decode_layers(_supported),
                                vly_decode_attention_merged; 6: vly_decode_layers(_supported) and tile hint 297 moved to the
                                EXPERIMENTAL library (libvalley_hip_exp.so, section at the end), vly_gemv_bf16 takes M <= 16; 7: + vly_split3_f32, vly_norm_split3_f32,
-                               tile hints 397 / 398 / 497 of vly_gemm_bf16 */
+                               tile hints 397 / 398 / 497 of vly_gemm_bf16; 8: vly_argmax takes per-row sampling parameters
+                               (vly_sample_row) and a draw counter */
 
 /* epilogues of vly_gemm_bf16 */
 #define VLY_EPI_NONE        0   /* C = A W^T (+bias) (+residual)                                   */
@@ -355,9 +356,27 @@ int vly_resize_v_norm(const uint8_t *in, const int32_t *bounds, const int32_t *t
 /* p[i] += delta for i < n (the device-side position counter of a captured decode step). */
 int vly_incr_i32(int32_t *p, int n, int delta, void *stream);
 
-/* argmax over the last dim of fp32 [M,N] (row stride ld >= N) -> int32 [M]; first maximal index.
- *   serve/model_worker.py:389-391. */
-int vly_argmax(const float *x, int32_t *idx, int M, int N, int ld, void *stream);
+/* Sampling parameters of one row of vly_argmax, in DEVICE memory (a captured decode step reads them at every replay,
+ * so new settings need no re-capture).  24 bytes. */
+typedef struct {
+    float    temperature;   /* < 1e-4: greedy row (first maximal index) */
+    int32_t  top_k;         /* <= 0: off; clamped to N */
+    float    top_p;         /* >= 1: off; must be > 0 */
+    uint32_t seed_lo, seed_hi;
+    int32_t  reserved;      /* 0 */
+} vly_sample_row;
+
+/* Token selection over the last dim of fp32 [M,N] (row stride ld >= N) -> int32 [M].
+ *   rows == NULL: argmax, the first maximal index (NaN never selected); serve/model_worker.py:389-391.
+ *   rows != NULL: rows[r] decides row r.  Greedy rows give the argmax above; the others draw one token, in HF's warper
+ *   order: s = x / T; top-k keeps s >= the k-th largest s (ties kept); top-p keeps token t iff the softmax mass of the
+ *   kept tokens strictly above s_t is < p; then Gumbel-max, argmax over kept i of s_i - log(-log(u_i)), first index on
+ *   ties.  u_i = (2 * (w >> 9) + 1) * 2^-24 with w = word i & 3 of Philox4x32-10 at key (seed_lo, seed_hi), counter
+ *   (i >> 2, c, 0, 0), where the draw counter c = (ctr ? ctr[ctr_per_row ? r : 0] : 0) + ctr_add is the index, in the
+ *   row's sequence, of the token being drawn.  A row without a finite kept score gives the argmax.  Deterministic: the
+ *   same inputs give the same tokens at every launch (sampling.hip). */
+int vly_argmax(const float *x, int32_t *idx, int M, int N, int ld, const vly_sample_row *rows, const int32_t *ctr,
+               int ctr_per_row, int ctr_add, void *stream);
 
 /* C[M,N] = epi(A[M,K] W[N,K]^T + bias), bf16 out, for FEW rows (M <= 256; N % 32 == 0; K % 128 == 0, K % 512 == 0 from
  *   K = 2048 on; epilogue NONE, QUICK_GELU or

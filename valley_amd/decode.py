@@ -3,7 +3,7 @@ valley/serve/model_worker.py:380-394 and of HF ``generate`` behind valley_model.
 
 One decode step = embedding gather of the current token -> L x [RMSNorm + q|k|v GEMV, RoPE + KV append +
 decode attention (every head split over four workgroups at batch <= 2), (merge +) o GEMV(+res), RMSNorm + gate/up GEMV with SwiGLU, down GEMV(+res)] -> RMSNorm +
-lm_head GEMV -> argmax -> position += 1.  Every kernel is HBM-bound weight/KV streaming, 5 launches
+lm_head GEMV -> argmax (or a seeded draw) -> position += 1.  Every kernel is HBM-bound weight/KV streaming, 5 launches
 per layer (the norms ride inside the GEMV that consumes them at batch <= 2; 7 otherwise): launched eagerly from Python the step would be host-bound (>300 launches x ~15 us), so the
 step is captured ONCE into a hipGraph and replayed.  Static shapes are what capture needs: the KV
 cache is pre-allocated to ctx_max, and the only thing that changes between replays — the position —
@@ -37,9 +37,14 @@ MERGE_IN = os.environ.get("VALLEY_DECODE_MERGE", "attn")
 SPLIT_ROWS = os.environ.get("VALLEY_DECODE_SPLIT_ROWS", "1") != "0"       # round 5: the merged split attention for 3 .. 8 rows as well
 
 class DecodeSession:
-    def __init__(self, llama: HipLlama, cache: HipKVCache, use_graph: bool = True, per_row_positions: bool = False):
+    def __init__(self, llama: HipLlama, cache: HipKVCache, use_graph: bool = True, per_row_positions: bool = False,
+                 sampling: bool = False):
         """``per_row_positions``: every batch row is an independent sequence at its own position (``pos`` is int32 [B]
-        and advances by one per step for every row) — the captured step of valley_amd.serving.ContinuousBatcher."""
+        and advances by one per step for every row) — the captured step of valley_amd.serving.ContinuousBatcher.
+        ``sampling``: the step draws each row's next token with that row's parameters in ``self.sample`` (int32 [B, 6],
+        ops.sampling_rows; all rows greedy until written) instead of taking the argmax.  The draw counter is the index of
+        the drawn token in the row's sequence (``pos + 1``), and ``self.sample`` is read at every replay: writing it
+        between steps changes the parameters without a re-capture."""
         self.ll, self.cache = llama, cache
         B, d = cache.batch, llama.device
         if B > 8:
@@ -48,6 +53,7 @@ class DecodeSession:
         self.per_row = per_row_positions
         self.tok = torch.zeros((B,), dtype=torch.int32, device=d)          # token fed to the next step
         self.pos = torch.zeros((B if per_row_positions else 1,), dtype=torch.int32, device=d)   # on the device: replays need no patching
+        self.sample = ops.sampling_rows([0.0] * B, device=d) if sampling else None
         self.h = torch.empty((B, llama.H), dtype=torch.float32, device=d)
         bf = runtime.HALF
         self.x = torch.empty((B, llama.H), dtype=bf, device=d)
@@ -122,9 +128,12 @@ class DecodeSession:
         else:
             ops.rmsnorm(self.h, ll.norm, ll.eps, out=self.x)
             ops.gemv(self.x, ll.lm_head, out=self.logits)
-        # greedy next token straight into the input slot of the next step (the V-padding columns of the
+        # greedy (or sampled) next token straight into the input slot of the next step (the V-padding columns of the
         # lm_head buffer are excluded through the row stride)
-        ops.argmax(self.logits[:, :ll.V], out=self.tok)
+        if self.sample is None:
+            ops.argmax(self.logits[:, :ll.V], out=self.tok)
+        else:
+            ops.argmax(self.logits[:, :ll.V], sampling=self.sample, ctr=self.pos, ctr_add=1, out=self.tok)
         ops.incr_i32(self.pos, 1)
 
     def begin(self, first_token: Optional[torch.Tensor] = None):

@@ -58,7 +58,7 @@ _SIGS = {
     "vly_pack_weight_bf16": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "vly_add2_rmsnorm": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_float, _P]),
     "vly_add2_layernorm": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_float, _P]),
-    "vly_argmax": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "vly_argmax": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_int, c_int, _P]),
     "vly_cast_f32_bf16": (c_int, [_P, _P, c_long, _P]),
     "vly_gemm_bf16_qkv_rope": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                        c_int, _P]),
@@ -76,7 +76,7 @@ _SIGS = {
     "vly_embed_splice_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, _P]),
 }
 EXPORTS = tuple(_SIGS)
-ABI_VERSION = 7
+ABI_VERSION = 8
 # include/valley_hip.h "EXPERIMENTAL entry points": exported by libvalley_hip_exp.so only (VALLEY_EXPERIMENTAL=1); bound when present
 _SIGS_EXPERIMENTAL = {
     "vly_decode_attention_split": (c_int, [_P, _P, _P, _P, _P, _P, c_int, _P, c_int, c_int, c_int, _P, c_int, c_int, _P]),

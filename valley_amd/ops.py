@@ -1110,14 +1110,81 @@ def decode_layers(table: torch.Tensor, h: torch.Tensor, qkv: torch.Tensor, parti
     return h
 
 
-def argmax(x: torch.Tensor, out=None) -> torch.Tensor:
-    """x fp32 [M,N] (row stride may exceed N) -> int32 [M]."""
+GREEDY_T = 1e-4          # temperatures below this select the first maximal logit (the reference worker's threshold)
+
+
+def sampling_rows(temperature, top_k=0, top_p=1.0, seed=0, device=None) -> torch.Tensor:
+    """Per-row sampling parameters of ``argmax`` (include/valley_hip.h ``vly_sample_row``) as an int32 [M, 6] device tensor:
+    temperature (fp32 bits), top_k, top_p (fp32 bits), seed low / high word, 0.  Each argument is a scalar (broadcast) or
+    a sequence of M values.  temperature < 1e-4 is a greedy row, top_k = 0 and top_p = 1 are off."""
+    def as_list(v, name):
+        if isinstance(v, torch.Tensor):
+            v = v.reshape(-1).tolist()
+        return list(v) if isinstance(v, (list, tuple)) else None
+
+    cols = {"temperature": temperature, "top_k": top_k, "top_p": top_p, "seed": seed}
+    lens = {len(v) for v in (as_list(c, n) for n, c in cols.items()) if v is not None}
+    if len(lens) > 1:
+        raise ValueError(f"sampling_rows: per-row arguments of different lengths {sorted(lens)}")
+    M = lens.pop() if lens else 1
+    if M < 1:
+        raise ValueError("sampling_rows: no rows")
+    vals = {n: (as_list(c, n) if as_list(c, n) is not None else [c] * M) for n, c in cols.items()}
+    import math
+    import numbers
+    for T in vals["temperature"]:
+        if isinstance(T, bool) or not (isinstance(T, numbers.Real) and math.isfinite(T) and T >= 0):
+            raise ValueError(f"sampling_rows: temperature must be finite and >= 0, got {T!r}")
+    for k in vals["top_k"]:
+        if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 0 <= k <= 0x7fffffff:
+            raise ValueError(f"sampling_rows: top_k must be an int >= 0, got {k!r}")
+    for p in vals["top_p"]:
+        if isinstance(p, bool) or not (isinstance(p, numbers.Real) and 0 < p <= 1):
+            raise ValueError(f"sampling_rows: top_p must be in (0, 1], got {p!r}")
+    for s in vals["seed"]:
+        if isinstance(s, bool) or not isinstance(s, numbers.Integral) or not 0 <= s < 1 << 64:
+            raise ValueError(f"sampling_rows: seed must be an int in [0, 2^64), got {s!r}")
+    t = torch.zeros((M, 6), dtype=torch.int32)
+    f = t.view(torch.float32)
+    f[:, 0] = torch.tensor([float(T) for T in vals["temperature"]], dtype=torch.float32)
+    t[:, 1] = torch.tensor([int(k) for k in vals["top_k"]], dtype=torch.int32)
+    f[:, 2] = torch.tensor([float(p) for p in vals["top_p"]], dtype=torch.float32)
+    lo = [int(s) & 0xffffffff for s in vals["seed"]]
+    hi = [int(s) >> 32 for s in vals["seed"]]
+    t[:, 3] = torch.tensor([v - (1 << 32) if v >= 1 << 31 else v for v in lo], dtype=torch.int32)
+    t[:, 4] = torch.tensor([v - (1 << 32) if v >= 1 << 31 else v for v in hi], dtype=torch.int32)
+    return t.to(device) if device is not None else t
+
+
+def argmax(x: torch.Tensor, out=None, sampling: Optional[torch.Tensor] = None, ctr: Optional[torch.Tensor] = None,
+           ctr_add: int = 0) -> torch.Tensor:
+    """x fp32 [M,N] (row stride may exceed N) -> int32 [M]: the first maximal index of every row, or — with ``sampling``
+    (int32 [M, 6] from ``sampling_rows``, on the device) — one seeded draw per row with that row's temperature / top-k /
+    top-p.  The draw counter of row r is ``ctr[r]`` (int32 [M]) or ``ctr[0]`` (int32 [1]), plus ``ctr_add``: the index,
+    in the row's sequence, of the token being drawn.  Everything is read on the device, so a captured launch replays
+    with new parameters / counters."""
     _chk(x, torch.float32, "x", contiguous=False)
     M, N = x.shape
     assert x.stride(1) == 1
     if out is None:
         out = torch.empty((M,), dtype=torch.int32, device=x.device)
-    rc = _lib.load().vly_argmax(x.data_ptr(), out.data_ptr(), M, N, x.stride(0), _stream())
+    _chk(out, torch.int32, "out")
+    assert out.numel() == M
+    rows = cptr = None
+    per_row = 0
+    if sampling is not None:
+        _chk(sampling, torch.int32, "sampling")
+        if tuple(sampling.shape) != (M, 6):
+            raise ValueError(f"argmax: sampling must be int32 [{M}, 6], got {tuple(sampling.shape)}")
+        rows = sampling.data_ptr()
+        if ctr is not None:
+            _chk(ctr, torch.int32, "ctr")
+            if ctr.numel() not in (1, M):
+                raise ValueError(f"argmax: ctr must hold 1 or {M} counters, got {ctr.numel()}")
+            cptr, per_row = ctr.data_ptr(), int(ctr.numel() == M and M > 1)
+    elif ctr is not None or ctr_add:
+        raise ValueError("argmax: a draw counter needs sampling parameters")
+    rc = _lib.load().vly_argmax(x.data_ptr(), out.data_ptr(), M, N, x.stride(0), rows, cptr, per_row, int(ctr_add), _stream())
     _lib.check(rc, "vly_argmax")
     return out
 

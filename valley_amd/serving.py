@@ -5,8 +5,9 @@ with greedy / temperature sampling, stop-token and stop-string handling, and ``j
 scope; this generator is what those routes would wrap.
 
 Decode steps run through the hipGraph-captured ``DecodeSession``: the greedy token never leaves the
-device between steps; with temperature sampling the step's logits are sampled by torch.multinomial (as in
-the reference) and the chosen token is written back into the session's input slot."""
+device between steps; with temperature sampling ``generate_video_stream`` samples the step's logits by
+torch.multinomial (as in the reference) and writes the chosen token back into the session's input slot,
+while a sampling ``ContinuousBatcher`` draws seeded tokens inside the captured step."""
 from __future__ import annotations
 
 import json
@@ -14,6 +15,7 @@ from typing import Iterator, Optional
 
 import torch
 
+from . import ops
 from .decode import DecodeSession
 from .valley_model import (DEFAULT_IM_END_TOKEN, DEFAULT_IM_START_TOKEN, DEFAULT_IMAGE_PATCH_TOKEN, DEFAULT_VI_END_TOKEN,
                            DEFAULT_VI_START_TOKEN, DEFAULT_VIDEO_FRAME_TOKEN, DEFAULT_VIDEO_TOKEN)
@@ -107,7 +109,10 @@ class ContinuousBatcher:
     slots are fully independent sequences: ``vly_decode_attention_rows``.  Idle slots run along (their rows are computed
     and ignored: the GEMV cost does not depend on the row count), clamped inside their cache rows."""
 
-    def __init__(self, model, slots: int = 4, ctx_max: int = 1024, use_graph: bool = True):
+    def __init__(self, model, slots: int = 4, ctx_max: int = 1024, use_graph: bool = True, sampling: bool = False):
+        """``sampling``: the captured step draws every slot's token with the parameters ``add`` gave its request
+        (temperature, top-k, top-p, seed; DecodeSession ``sampling``) — a seeded request's tokens then depend on its seed
+        alone, not on its slot or its neighbours.  Greedy requests take the argmax in either kind of batcher."""
         if not 1 <= slots <= 8:
             raise ValueError("1 <= slots <= 8 (the decode step streams weights with the GEMV kernels)")
         self.model, self.ll = model, model.get_model().llama
@@ -118,7 +123,8 @@ class ContinuousBatcher:
         self.full = []                                           # slots released by step() because their cache rows filled up
         self.cache = self.ll.new_cache(slots, ctx_max)
         self.cache.key_valid = torch.ones((slots, ctx_max), dtype=torch.uint8, device=self.ll.device)
-        self.sess = DecodeSession(self.ll, self.cache, use_graph=use_graph, per_row_positions=True)
+        self.sampling = sampling
+        self.sess = DecodeSession(self.ll, self.cache, use_graph=use_graph, per_row_positions=True, sampling=sampling)
         self.live = [False] * slots
         self.length = [0] * slots                                # tokens in each slot's cache (host mirror of sess.pos)
         self._captured = False
@@ -126,9 +132,19 @@ class ContinuousBatcher:
     def free_slots(self):
         return [i for i, v in enumerate(self.live) if not v]
 
-    def add(self, input_ids, images=None, attention_mask=None, first_token: Optional[int] = None) -> int:
+    def add(self, input_ids, images=None, attention_mask=None, first_token: Optional[int] = None, temperature: float = 0.0,
+            top_k: int = 0, top_p: float = 1.0, seed: Optional[int] = None) -> int:
         """Prefill one request (input_ids [1, S]) into a free slot; returns the slot.  The first generated token is the
-        prefill's argmax unless ``first_token`` is given (a caller that samples)."""
+        prefill's argmax unless ``first_token`` is given.  ``temperature`` >= 1e-4 (a sampling batcher only) makes the
+        request sample: its first token is drawn on the device from the prefill's logits (draw counter S), the following
+        ones inside the captured step; without a ``seed`` one is drawn from torch's generator."""
+        if temperature > 0 and not self.sampling:
+            raise ValueError("add(temperature > 0) needs ContinuousBatcher(..., sampling=True)")
+        params = None
+        if self.sampling:
+            if seed is None:
+                seed = int(torch.randint(0, 1 << 62, (1,)).item()) if temperature >= ops.GREEDY_T else 0
+            params = ops.sampling_rows(float(temperature), top_k, top_p, seed, device=self.ll.device)   # validates
         free = self.free_slots()
         if not free:
             raise RuntimeError("no free slot")
@@ -140,7 +156,14 @@ class ContinuousBatcher:
         self.cache.key_valid[slot] = 1
         row = type(self.cache).rows_of(self.cache, slot, slot + 1)
         out = self.model(input_ids=ids, images=images, attention_mask=attention_mask, past_key_values=row, use_cache=True)
-        tok = int(out.logits[0, -1].argmax()) if first_token is None else int(first_token)
+        if first_token is not None:
+            tok = int(first_token)
+        elif params is not None and temperature >= ops.GREEDY_T:
+            tok = int(ops.argmax(out.logits[0, -1:], sampling=params, ctr_add=S)[0])
+        else:
+            tok = int(out.logits[0, -1].argmax())
+        if params is not None:
+            self.sess.sample[slot:slot + 1].copy_(params)
         self.sess.pos[slot:slot + 1].fill_(S)
         self.sess.tok[slot:slot + 1].fill_(tok)
         self.live[slot], self.length[slot] = True, S
@@ -148,8 +171,8 @@ class ContinuousBatcher:
         return slot
 
     def step(self) -> dict:
-        """One decode step for every live slot: feeds each slot's current token, returns {slot: next greedy token}.
-        ``self.sess.logits[slot, :V]`` holds that slot's logits (a sampling caller overwrites ``self.sess.tok[slot]``)."""
+        """One decode step for every live slot: feeds each slot's current token, returns {slot: next token} (greedy, or
+        drawn with the slot's parameters in a sampling batcher).  ``self.sess.logits[slot, :V]`` holds that slot's logits."""
         if not self._captured:
             self.sess.begin()
             self._captured = True

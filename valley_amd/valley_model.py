@@ -586,21 +586,38 @@ class ValleyLlamaForCausalLM:
 
     @torch.no_grad()
     def generate(self, input_ids, images=None, attention_mask=None, max_new_tokens: int = 64, do_sample: bool = False,
-                 temperature: float = 1.0, stopping_criteria=None, eos_token_id=None, use_graph=True, **kw):
+                 temperature: float = 1.0, stopping_criteria=None, eos_token_id=None, use_graph=True, top_k=None, top_p=None,
+                 seed=None, **kw):
         """Prefill + per-token KV decode (the loop of serve/model_worker.py:371-394; the reference's CLI
         path reaches the same through HF ``generate``, valley_model.py:432).  Greedy when not sampling or
         temperature < 1e-4, else temperature softmax + multinomial.  Decode steps run through a
         hipGraph-captured DecodeSession (``use_graph=True``), eagerly through it (False) or through the
-        generic forward (None)."""
+        generic forward (None).
+
+        Sampling with any of ``top_k`` / ``top_p`` / ``seed`` given draws every token on the device (ops.argmax with
+        sampling parameters, inside the captured step): HF's temperature -> top-k -> top-p order, Gumbel-max with
+        Philox noise.  ``seed`` is an int (row r uses seed + r) or a list of B ints; the same seed gives the same
+        sequence in graph, eager and generic-forward decoding.  Without a seed one is drawn from torch's generator."""
         input_ids = input_ids.to(self.device)
         B, S = input_ids.shape
         ctx = min(getattr(self.config, "max_position_embeddings", 2048), S + max_new_tokens)
         cache = self.model.llama.new_cache(B, max(ctx, S + 1))
         out = self.forward(input_ids=input_ids, images=images, attention_mask=attention_mask, past_key_values=cache,
                            use_cache=True)
-        greedy = not (do_sample and temperature >= 1e-4)
+        greedy = not (do_sample and temperature >= ops.GREEDY_T)
+        sample = None                                        # per-row parameters of the on-device draw
+        if not greedy and (top_k is not None or top_p is not None or seed is not None):
+            if seed is None:
+                seed = int(torch.randint(0, 1 << 62, (1,)).item())       # reproducible under torch.manual_seed
+            seeds = [(int(seed) + r) % (1 << 64) for r in range(B)] if not isinstance(seed, (list, tuple)) else list(seed)
+            if len(seeds) != B:
+                raise ValueError(f"generate: {len(seeds)} seeds for {B} rows")
+            sample = ops.sampling_rows(float(temperature), 0 if top_k is None else top_k, 1.0 if top_p is None else top_p,
+                                       seeds, device=self.device)
 
-        def pick(last):
+        def pick(last, ctr):
+            if sample is not None:                           # ctr: index of the drawn token in the sequence
+                return ops.argmax(last, sampling=sample, ctr_add=ctr).to(torch.long)
             return ops.argmax(last).to(torch.long) if greedy else \
                 torch.multinomial(torch.softmax(last / temperature, dim=-1), num_samples=1).view(B)
 
@@ -611,14 +628,16 @@ class ValleyLlamaForCausalLM:
         if pad is None:
             pad = int(eos[0]) if eos is not None else 0
         finished = torch.zeros((B,), dtype=torch.bool, device=self.device)     # HF: a finished row emits pad from then on
-        token = pick(out.logits[:, -1, :].contiguous())
+        token = pick(out.logits[:, -1, :].contiguous(), S)
         seq = torch.cat([input_ids, token[:, None]], dim=1)
         if B > 8 or self.model.precision == "fp32":
             use_graph = None                                 # the GEMV decode session is bf16, for <= 8 sequences
         sess = None
         if use_graph is not None:
             from .decode import DecodeSession
-            sess = DecodeSession(self.model.llama, cache, use_graph=bool(use_graph))
+            sess = DecodeSession(self.model.llama, cache, use_graph=bool(use_graph), sampling=sample is not None)
+            if sample is not None:
+                sess.sample.copy_(sample)
             sess.begin(token)
         mask = attention_mask
         for _ in range(max_new_tokens - 1):
@@ -634,18 +653,18 @@ class ValleyLlamaForCausalLM:
                 break
             if sess is not None:
                 nxt = sess.step()
-                if greedy:
+                if greedy or sample is not None:
                     token = nxt.to(torch.long).clone()
                 else:
-                    token = pick(sess.logits[:, :self.model.llama.V])
-                if bool(finished.any()) or not greedy:
+                    token = pick(sess.logits[:, :self.model.llama.V], None)
+                if bool(finished.any()) or not (greedy or sample is not None):
                     token = torch.where(finished, torch.full_like(token, pad), token)
                     sess.tok.copy_(token.to(torch.int32))
             else:
                 if mask is not None:
                     mask = torch.cat([mask.to(self.device), torch.ones((B, 1), dtype=mask.dtype, device=self.device)], dim=1)
                 out = self.forward(input_ids=token[:, None], attention_mask=mask, past_key_values=cache, use_cache=True)
-                token = torch.where(finished, torch.full_like(token, pad), pick(out.logits[:, -1, :].contiguous()))
+                token = torch.where(finished, torch.full_like(token, pad), pick(out.logits[:, -1, :].contiguous(), cache.seq_len))
             seq = torch.cat([seq, token[:, None]], dim=1)
         ops.sk_poll_async(self.device)
         torch.cuda.current_stream().synchronize()            # the caller decodes the tokens next; a stream-K hand-off
