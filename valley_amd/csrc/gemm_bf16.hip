@@ -173,11 +173,18 @@ constexpr int P4_M0_LEAD = 2;       // the M0 write of a piece sits this many MF
 #else
 #define VLY_MFMA16_NAME "v_mfma_f32_16x16x32_bf16"
 #endif
+// Blocks 64 .. 71 (only the 192 x 384 tile has them: 6 x 12 blocks per wave) are ARCH VGPRs v[VLY_VACC0 + 4 (blk - 64) ..], named the
+// same way and reserved the same way: one clobber list at the kernel's entry (VLY_VACC_VGPRS) makes the descriptor allocate v224 .. v255.
+// The compiler's own values need v0 .. v193 there and stay below v224; valley_amd/agpr_audit.py fails the build if any instruction
+// outside the asm ever names v224 .. v255 (an amdgpu_num_vgpr cap cannot be given to one instantiation of a kernel template).
+constexpr int VLY_VACC0 = 224;
 VLY_DEVICE void mfma16_lit(int blk, const bf16x8& a, const bf16x8& b) {          // a[4 blk ..] += A . B   (blk: constant after unrolling)
-    asm volatile(VLY_MFMA16_NAME " a[%2:%3], %0, %1, a[%2:%3]" ::"v"(a), "v"(b), "i"(4 * blk), "i"(4 * blk + 3));
+    if (blk < 64) asm volatile(VLY_MFMA16_NAME " a[%2:%3], %0, %1, a[%2:%3]" ::"v"(a), "v"(b), "i"(4 * blk), "i"(4 * blk + 3));
+    else asm volatile(VLY_MFMA16_NAME " v[%2:%3], %0, %1, v[%2:%3]" ::"v"(a), "v"(b), "i"(VLY_VACC0 + 4 * (blk - 64)), "i"(VLY_VACC0 + 4 * (blk - 64) + 3));
 }
 VLY_DEVICE void mfma16_lit_zero(int blk, const bf16x8& a, const bf16x8& b) {     // a[4 blk ..]  = A . B
-    asm volatile(VLY_MFMA16_NAME " a[%2:%3], %0, %1, 0" ::"v"(a), "v"(b), "i"(4 * blk), "i"(4 * blk + 3));
+    if (blk < 64) asm volatile(VLY_MFMA16_NAME " a[%2:%3], %0, %1, 0" ::"v"(a), "v"(b), "i"(4 * blk), "i"(4 * blk + 3));
+    else asm volatile(VLY_MFMA16_NAME " v[%2:%3], %0, %1, 0" ::"v"(a), "v"(b), "i"(VLY_VACC0 + 4 * (blk - 64)), "i"(VLY_VACC0 + 4 * (blk - 64) + 3));
 }
 VLY_DEVICE f32x4 acc_read_lit(int blk) {
     f32x4 v;
@@ -186,11 +193,22 @@ VLY_DEVICE f32x4 acc_read_lit(int blk) {
                  : "i"(4 * blk), "i"(4 * blk + 1), "i"(4 * blk + 2), "i"(4 * blk + 3));
     return v;
 }
+VLY_DEVICE f32x4 acc_read_vlit(int blk) {                                           // (blk >= 64: the block in arch VGPRs)
+    f32x4 v;
+    asm volatile("v_mov_b32 %0, v[%4]\n\tv_mov_b32 %1, v[%5]\n\tv_mov_b32 %2, v[%6]\n\tv_mov_b32 %3, v[%7]"
+                 : "=v"(v[0]), "=v"(v[1]), "=v"(v[2]), "=v"(v[3])
+                 : "i"(VLY_VACC0 + 4 * (blk - 64)), "i"(VLY_VACC0 + 4 * (blk - 64) + 1), "i"(VLY_VACC0 + 4 * (blk - 64) + 2),
+                   "i"(VLY_VACC0 + 4 * (blk - 64) + 3));
+    return v;
+}
 #define VLY_A8(n) "a" #n "0", "a" #n "1", "a" #n "2", "a" #n "3", "a" #n "4", "a" #n "5", "a" #n "6", "a" #n "7", "a" #n "8", "a" #n "9"
 #define VLY_ALL_AGPRS                                                                                                                  \
     "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", VLY_A8(1), VLY_A8(2), VLY_A8(3), VLY_A8(4), VLY_A8(5), VLY_A8(6), VLY_A8(7), \
         VLY_A8(8), VLY_A8(9), VLY_A8(10), VLY_A8(11), VLY_A8(12), VLY_A8(13), VLY_A8(14), VLY_A8(15), VLY_A8(16), VLY_A8(17), VLY_A8(18),   \
         VLY_A8(19), VLY_A8(20), VLY_A8(21), VLY_A8(22), VLY_A8(23), VLY_A8(24), "a250", "a251", "a252", "a253", "a254", "a255"
+#define VLY_V8(n) "v" #n "0", "v" #n "1", "v" #n "2", "v" #n "3", "v" #n "4", "v" #n "5", "v" #n "6", "v" #n "7", "v" #n "8", "v" #n "9"
+#define VLY_VACC_VGPRS                                                                                                                 \
+    "v224", "v225", "v226", "v227", "v228", "v229", VLY_V8(23), VLY_V8(24), "v250", "v251", "v252", "v253", "v254", "v255"
 
 // MODE: 0 = builtin accumulate into acc[][]; 2 / 3 = accumulators by name: accumulate / first K step of a tile (C = 0)
 template <int MI, int NI, int N1, int S1, int D1, int N2, int S2, int D2, int N3, int S3, int D3, int N4, int S4, int D4, int MODE = 0,
@@ -1011,6 +1029,7 @@ gemm_p4_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ W, c
     constexpr int WM = BM / 2, WN = BN / 2, NT = 256;
     constexpr bool SKT = SK && BM != 256;       // the owner's epilogue adds slab terms (256-row tiles fold them into the accumulators instead)
     constexpr int MI = WM / 16, NI = WN / 16;
+    constexpr bool VACC = MI * NI > 64;         // accumulator blocks 64 .. in arch VGPRs (192 x 384, by name, unrolled schedule only)
     constexpr int A_BYTES = BM * 128, W_BYTES = BN * 128, STAGE = A_BYTES + W_BYTES;
     constexpr int PA = BM * 8 / NT, PW = BN * 8 / NT, NS = PA + PW;
     static_assert(BM * 8 % NT == 0 && BN * 8 % NT == 0 && NI % 4 == 0, "tile/threads mismatch");
@@ -1217,7 +1236,10 @@ gemm_p4_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ W, c
     constexpr bool ROLL = VLY_P4_ROLL != 0 && LIT && !CHAIN && ((VLY_P4_ROLL_MASK >> EPI) & 1) != 0;
     constexpr int NST_ = EPI == VLY_EPI_SWIGLU ? NI / 4 : NI / 2;    // 16-byte stores per fragment row of the bf16 epilogue
     static_assert(!ROLL || N1 + MI * NST_ <= 63, "vmcnt is a 6-bit count");
+    static_assert(!VACC || (LIT && !ROLL && !CHAIN && EPI == VLY_EPI_SWIGLU && MI * NI <= 64 + (256 - VLY_VACC0) / 4),
+                  "VGPR accumulator blocks: by name, unrolled schedule, SwiGLU epilogue");
     if constexpr (LIT) asm volatile("" ::: VLY_ALL_AGPRS);           // the kernel owns a0 .. a255 (this is what makes the descriptor allocate them)
+    if constexpr (VACC) asm volatile("" ::: VLY_VACC_VGPRS);         // ... and v224 .. v255 (see mfma16_lit)
     f32x4 acc[MI][NI];                                               // (untouched, and optimised away, when LIT)
     bool wave_live = false;                                          // this wave's slab of the tile being computed lies inside the problem
     // first_c: the first K tile of a tile.  relaxed (ROLL): the first K tile after a boundary — the stream of vector-memory operations
@@ -1390,6 +1412,11 @@ gemm_p4_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ W, c
                     for (int jj = 0; jj < 4; ++jj) {
                         if constexpr (SKT) {
                             const f32x4 v = acc_read(acc[i][4 * jq + jj]) + slab_term(i, 4 * jq + jj);
+                            gt[jj] = f32x2{v[0], v[2]};
+                            up[jj] = f32x2{v[1], v[3]};
+                        } else if constexpr (VACC) {
+                            const int blk = i * NI + 4 * jq + jj;
+                            const f32x4 v = blk < 64 ? acc_read_lit(blk) : acc_read_vlit(blk);
                             gt[jj] = f32x2{v[0], v[2]};
                             up[jj] = f32x2{v[1], v[3]};
                         } else if constexpr (LIT) {
@@ -1880,6 +1907,14 @@ gemm_p4_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ W, c
 }
 #undef VLY_STAMP
 
+// the 192 x 384 instantiation (tile hint 194) on the unrolled by-name schedule only: A/B builds that change the schedule leave it out (hint
+// 194 then runs hint 197), and so do the VLY_FEW_TILES builds (their switch does not name it)
+#ifdef VLY_FEW_TILES
+#define VLY_P4V 0
+#else
+#define VLY_P4V (VLY_P4_LIT != 0 && VLY_P4_CHAIN == 0 && !(VLY_P4_ROLL != 0 && ((VLY_P4_ROLL_MASK >> VLY_EPI_SWIGLU) & 1)))
+#endif
+
 #if VLY_P4_TIMING
 static void* vlydbg_p4_buffer() {
     static void* buf = [] { void* p = nullptr; (void)hipMalloc(&p, 64 * 65 * 8); (void)hipMemset(p, 0, 64 * 65 * 8); return p; }();
@@ -1896,6 +1931,17 @@ struct P4SkArgs {                                          // split-K remainder 
     int slab_cap;                                          // slabs the workspace holds
 };
 
+int p4_cus() {                                                          // workgroups of a persistent launch
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        (void)hipGetDevice(&dev);
+        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+        if (getenv("VLY_P4_GRID")) n = atoi(getenv("VLY_P4_GRID"));
+        return n > 0 ? n / 8 * 8 : 256;                                // a multiple of the XCD count (tile -> XCD mapping)
+    }();
+    return cus;
+}
+
 template <int BM, int BN, bool SK = false>
 int launch_p4(const void* A, const void* W, const float* bias, const float* R, void* C, int M, int N, int K, int lda, int ldw,
               int ldc, int ldr, int epi, int out, hipStream_t st, const RopeArgs* rope = nullptr, const P4SkArgs* sk = nullptr) {
@@ -1906,13 +1952,7 @@ int launch_p4(const void* A, const void* W, const float* bias, const float* R, v
     const int vec_ok = (out == VLY_OUT_BF16 && ldc % 8 == 0 && ((uintptr_t)C & 15) == 0 && !R && No % 8 == 0 &&
                         (size_t)M * (size_t)ldc * 2 < ((size_t)1 << 31)) ? 1 : 0;
     if (out == VLY_OUT_BF16 && !vec_ok) return 1;                       // caller falls back to the one-tile-per-workgroup kernel
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        if (getenv("VLY_P4_GRID")) n = atoi(getenv("VLY_P4_GRID"));
-        return n > 0 ? n / 8 * 8 : 256;                                // a multiple of the XCD count (tile -> XCD mapping)
-    }();
+    const int cus = p4_cus();
     const int tiles = tm * tn;
     // SK: slices per remainder tile — the S that packs S x rem8 units into the fewest rounds per slice (1 = no split), within
     // the slab capacity, at least two K tiles per slice, +6 % of a tile per extra slice for the hand-off chain and the shallower
@@ -1951,6 +1991,26 @@ int launch_p4(const void* A, const void* W, const float* bias, const float* R, v
     }
 #undef VLY_P4_LAUNCH
     return vly_check_launch("vly_gemm_bf16");
+}
+
+// tile hint 194 (gemm_p4_kernel<192, 384, SwiGLU>): 1 = not its problem — another epilogue or output, a bias or residual, rows that the 16-byte
+// stores cannot take, or an A/B build without the kernel; the caller then runs hint 197
+int launch_p4v(const void* A, const void* W, const float* bias, const float* R, void* C, int M, int N, int K, int lda, int ldw, int ldc,
+               int ldr, int epi, int out, hipStream_t st) {
+#if VLY_P4V
+    constexpr int BM = 192, BN = 384;
+    if (epi != VLY_EPI_SWIGLU || out != VLY_OUT_BF16 || bias || R || ldc % 8 || ((uintptr_t)C & 15) || (N >> 1) % 8 ||
+        (size_t)M * (size_t)ldc * 2 >= ((size_t)1 << 31))
+        return 1;
+    const int tm = (M + BM - 1) / BM, tn = (N + BN - 1) / BN, tiles = tm * tn, cus = p4_cus();
+    const int gm = vly_tile_group_height(M, N, K, tm, tn, BM, BN, 1);
+    hipLaunchKernelGGL((gemm_p4_kernel<BM, BN, VLY_EPI_SWIGLU, VLY_OUT_BF16, false>), dim3(tiles >= cus ? cus : tiles), dim3(256), 0, st, (const uint16_t*)A, (const uint16_t*)W, bias, R, C,
+                       M, N, K, lda, ldw, ldc, ldr, tm, tn, gm, RopeArgs{}, nullptr, nullptr, 0u, 1);
+    return vly_check_launch("vly_gemm_bf16");
+#else
+    (void)A, (void)W, (void)bias, (void)R, (void)C, (void)M, (void)N, (void)K, (void)lda, (void)ldw, (void)ldc, (void)ldr, (void)epi, (void)out, (void)st;
+    return 1;
+#endif
 }
 
 template <int BM, int BN, int WM, int WN, int PIPE>
@@ -2132,6 +2192,12 @@ static int run_tile(int t, int tile_hint, const void* A, const void* W, const fl
                                           : launch_p4<192, 256>(A, W, bias, residual, C, M, N, K, lda, ldw, ldc, ldr, epilogue, out_dtype, st, rope);
                 // 1: bf16 rows that are not 16-byte aligned, or bf16 + residual -> the LDS / fragment epilogues of tile 97 / 98
                 return rc == 1 ? run_tile(t - 100, tile_hint, VLY_TILE_ARGS_RAW) : rc;
+            }
+        case 194:                                           // persistent 192 x 384, SwiGLU only (launch_p4v); what it does not take goes to 197
+            if (C2) { vly_set_error("vly_gemm_bf16: tile_hint %d does not take the split-K pair", tile_hint); return -22; }
+            {
+                const int rc = K < 2 * BK || rope ? 1 : launch_p4v(A, W, bias, residual, C, M, N, K, lda, ldw, ldc, ldr, epilogue, out_dtype, st);
+                return rc == 1 ? run_tile(197, tile_hint, VLY_TILE_ARGS_RAW) : rc;
             }
         case 97:
         case 98:                                            // 224 x 256 (M = 2688 = 12 x 224), 112 x 128 per wave

@@ -117,7 +117,14 @@ def _gemm_common(fn_name, a, w, bias, residual, epilogue, out_dtype, out, extra)
             out.stride(0), residual.stride(0) if residual is not None else 0, epilogue, od, *extra, _stream())
     if rec is not None:
         e1.record()
-        if sk and tile in (297, 298, 299):
+        # hint 194 (the 192 x 384 persistent tile) takes SwiGLU into aligned bf16 rows only; anything else runs hint 197
+        p4v = (not sk and tile == 194 and epilogue == EPI_SWIGLU and od == OUT_BF16 and bias is None and residual is None and K >= 128
+               and out.stride(0) % 8 == 0 and out.data_ptr() % 16 == 0)
+        if not sk and tile == 194 and not p4v:
+            tile = 197
+        if p4v:
+            name = f"gemm_p4_kernel<192, 384, {epilogue}, {od}, false>"
+        elif sk and tile in (297, 298, 299):
             name = f"gemm_p4_kernel<{TILE_SPECIAL[tile - 100][0][3:]}, {epilogue}, {od}, true>"     # (the names rocprofv3 prints)
         elif sk:
             name = f"gemm_sk_kernel<{TILE_NAMES[tile]}, {epilogue}, {od}, {sk_loop}>"
@@ -418,7 +425,7 @@ def _flush_caches(device):
     buf.zero_()
 
 
-CANDIDATES = [("tile", t) for t in (1, 2, 3, 4, 5, 6, 7, 8, 9, 51, 53, 54, 55, 73, 74, 76, 83, 84, 86, 93, 94, 97, 98, 99, 197, 198, 199)] + \
+CANDIDATES = [("tile", t) for t in (1, 2, 3, 4, 5, 6, 7, 8, 9, 51, 53, 54, 55, 73, 74, 76, 83, 84, 86, 93, 94, 97, 98, 99, 194, 197, 198, 199)] + \
              [("sk", t) for t in (51, 55, 73, 74, 76, 83, 84, 86, 151, 155, 183, 184, 186, 298, 299)] + \
              ([("sk", 297)] if _lib.EXPERIMENTAL else [])    # (297: the experimental library's split-K remainder on 256-row tiles)
 TUNE_TRIALS = int(os.environ.get("VALLEY_TUNE_TRIALS", "3"))
