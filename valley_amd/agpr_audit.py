@@ -77,6 +77,32 @@ def audit_asm(asm_path, kern):
     return report, kernels, bad
 
 
+def audit_plain(asm_path):
+    """Kernels that own no accumulation register by name (the beam-search library): no instruction of any kernel names an
+    accumulation register or touches scratch.  -> (lines of report, number of kernels, number of findings)"""
+    asm = open(asm_path).read().splitlines()
+    areg = re.compile(r"\ba(\[(\d+|0x[0-9a-f]+)(:(\d+|0x[0-9a-f]+))?\]|\d+\b)")
+    report, kernels, bad = [], 0, 0
+    i = 0
+    while i < len(asm):
+        m = re.match(r"^(_Z\S*kernel\S*):", asm[i])
+        if not m:
+            i += 1
+            continue
+        j, found = i + 1, []
+        while j < len(asm) and "s_endpgm" not in asm[j]:
+            code = asm[j].split(";")[0]
+            if (areg.search(code) and not code.strip().startswith(".")) or "scratch_" in code or "v_accvgpr" in code:
+                found.append((j - i, code.strip()))
+            j += 1
+        kernels += 1
+        bad += len(found)
+        report.append(f"{m.group(1)[:60]:60s} accumulation-register / scratch instructions: {len(found)}  {'FAIL' if found else 'ok'}")
+        report += [f"    +{off}: {code}" for off, code in found[:8]]
+        i = j
+    return report, kernels, bad
+
+
 _VREG = re.compile(r"\bv(?:\[(\d+|0x[0-9a-f]+)(?::(\d+|0x[0-9a-f]+))?\]|(\d+)\b)")
 
 

@@ -16,6 +16,10 @@ LIB_F16 = os.path.join(LIBDIR, "libvalley_hip_f16.so")      # the same sources w
 LIB_EXP = os.path.join(LIBDIR, "libvalley_hip_exp.so")
 LIB_EXP_F16 = os.path.join(LIBDIR, "libvalley_hip_exp_f16.so")   # the same on fp16 storage (the experiments' bit-identity tests run on both types)
 EXP_UNITS = ["decode_step.hip", "attention.hip", "gemm_bf16.hip", "gemv_bf16.hip"]
+# the beam-search kernels (include/valley_hip_beam.h): a companion library of their own, independent of the storage type — one
+# build serves the bf16 and fp16 libraries and the fp32 engine; the shipped libraries' exports stay exactly valley_hip.h's
+LIB_BEAM = os.path.join(LIBDIR, "libvalley_hip_beam.so")
+BEAM_SOURCES = ["beam.hip"]
 SOURCES = ["capi.hip", "gemm_bf16.hip", "gemm_p32.hip", "gemm_p16.hip", "gemm_streamk.hip", "norm_elementwise.hip", "attention.hip", "temporal_delta.hip", "preprocess.hip", "gemv_bf16.hip", "precise_f32.hip", "gemm_skinny.hip", "decode_step.hip", "sampling.hip"]
 
 
@@ -30,8 +34,9 @@ def hipcc() -> str:
 
 
 def needs_build() -> bool:
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "valley_hip.h")]
-    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16):
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h)
+                                                                 for h in ("valley_hip.h", "valley_hip_beam.h")]
+    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, LIB_BEAM):
         if not os.path.exists(lib):
             return True
         t = os.path.getmtime(lib)
@@ -46,16 +51,17 @@ def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(os.path.join(LIBDIR, "f16"), exist_ok=True)
     os.makedirs(os.path.join(LIBDIR, "exp"), exist_ok=True)
     os.makedirs(os.path.join(LIBDIR, "exp_f16"), exist_ok=True)
+    os.makedirs(os.path.join(LIBDIR, "beam"), exist_ok=True)
     if not force and not needs_build():
         return LIB
     variants = [(LIB, LIBDIR, [], SOURCES), (LIB_F16, os.path.join(LIBDIR, "f16"), ["-DVLY_FP16=1"], SOURCES),
                 (LIB_EXP, os.path.join(LIBDIR, "exp"), ["-DVLY_EXPERIMENTAL=1"], EXP_UNITS),
                 (LIB_EXP_F16, os.path.join(LIBDIR, "exp_f16"), ["-DVLY_EXPERIMENTAL=1", "-DVLY_FP16=1"], EXP_UNITS)]
     try:
-        from .agpr_audit import AUDITED, audit_asm
+        from .agpr_audit import AUDITED, audit_asm, audit_plain
     except ImportError:                                                   # (run as a script: python valley_amd/build.py)
         sys.path.insert(0, HERE)
-        from agpr_audit import AUDITED, audit_asm
+        from agpr_audit import AUDITED, audit_asm, audit_plain
     jobs, audits = [], []
     # a translation unit is recompiled when its own source, a shared header (*.hpp, *.inc, valley_hip.h) or this recipe is newer than
     # its object — editing one kernel file costs one compile per library, not twenty-two
@@ -73,6 +79,15 @@ def build(force: bool = False, verbose: bool = True) -> str:
             jobs.append((s, cmd))
             if s in AUDITED:
                 audits.append((s, odir, " ".join(flags) or "(default flags)"))
+    beam_dir = os.path.join(LIBDIR, "beam")
+    for s in BEAM_SOURCES:
+        o = os.path.join(beam_dir, s.replace(".hip", ".o"))
+        t_dep = max(os.path.getmtime(os.path.join(CSRC, s)), os.path.getmtime(os.path.abspath(__file__)),
+                    os.path.getmtime(os.path.join(HERE, "..", "include", "valley_hip_beam.h")))
+        if force or not os.path.exists(o) or os.path.getmtime(o) < t_dep:
+            jobs.append((s, [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-save-temps=obj", "-c",
+                             os.path.join(CSRC, s), "-o", o]))
+            audits.append((s, beam_dir, "(companion library)"))
     running = []
     while jobs or running:
         while jobs and len(running) < MAX_PARALLEL:
@@ -90,7 +105,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
     for s, odir, what in audits:
         stem = os.path.join(odir, s[:-4])
         asm = stem + "-hip-amdgcn-amd-amdhsa-gfx950.s"
-        report, kernels, bad = audit_asm(asm, AUDITED[s])
+        # the companion library's kernels own no accumulation register: none may be named at all, and no scratch
+        report, kernels, bad = audit_asm(asm, AUDITED[s]) if s in AUDITED else audit_plain(asm)
         for ext in ("-hip-amdgcn-amd-amdhsa-gfx950.s", "-hip-amdgcn-amd-amdhsa-gfx950.bc", "-hip-amdgcn-amd-amdhsa-gfx950.hipi",
                     "-hip-amdgcn-amd-amdhsa-gfx950.o", "-hip-amdgcn-amd-amdhsa-gfx950.out", "-hip-amdgcn-amd-amdhsa-gfx950.out.resolution.txt",
                     "-host-x86_64-unknown-linux-gnu.bc", "-host-x86_64-unknown-linux-gnu.hipi", "-host-x86_64-unknown-linux-gnu.s",
@@ -111,6 +127,11 @@ def build(force: bool = False, verbose: bool = True) -> str:
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
+    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_BEAM] + \
+        [os.path.join(LIBDIR, "beam", s.replace(".hip", ".o")) for s in BEAM_SOURCES]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
     return LIB
 
 

@@ -38,13 +38,19 @@ SPLIT_ROWS = os.environ.get("VALLEY_DECODE_SPLIT_ROWS", "1") != "0"       # roun
 
 class DecodeSession:
     def __init__(self, llama: HipLlama, cache: HipKVCache, use_graph: bool = True, per_row_positions: bool = False,
-                 sampling: bool = False):
+                 sampling: bool = False, beams: Optional[tuple] = None):
         """``per_row_positions``: every batch row is an independent sequence at its own position (``pos`` is int32 [B]
         and advances by one per step for every row) — the captured step of valley_amd.serving.ContinuousBatcher.
         ``sampling``: the step draws each row's next token with that row's parameters in ``self.sample`` (int32 [B, 6],
         ops.sampling_rows; all rows greedy until written) instead of taking the argmax.  The draw counter is the index of
         the drawn token in the row's sequence (``pos + 1``), and ``self.sample`` is read at every replay: writing it
-        between steps changes the parameters without a re-capture."""
+        between steps changes the parameters without a re-capture.
+        ``beams = (B, nb, S, eos_ids[, tail])``: beam search over the cache's B * nb rows (prompt b in rows b * nb ..), whose
+        shared prompt positions are [0, S).  Where the argmax ran, the step runs ops.beam_candidates over the running
+        scores in ``self.running`` (into ``self.cand``: score, token, parent row, hit — K per prompt) and then, with
+        ``tail`` (default True: the hits are the EOS ids), the rest of the step: ops.beam_select into ``self.tok`` /
+        ``self.parent`` / ``self.running``, ops.kv_beam_reorder of the generated positions [S, pos + 1) and pos += 1.
+        Without ``tail`` the caller writes its own hit mask into ``self.cand[3]`` and calls ``beam_tail()`` after each step."""
         self.ll, self.cache = llama, cache
         B, d = cache.batch, llama.device
         if B > 8:
@@ -72,6 +78,23 @@ class DecodeSession:
             self.sync = torch.zeros((ops.DECODE_SYNC_WORDS,), dtype=torch.int32, device=d)
             self.table = None
             self._table_gen = None
+        self.beams = None
+        if beams is not None:
+            if per_row_positions or sampling:
+                raise ValueError("beam sessions share one position and select deterministically")
+            bB, nb, S, eos = beams[:4]
+            if bB * nb != B:
+                raise ValueError(f"beam session: {bB} prompts x {nb} beams != {B} cache rows")
+            self.beams = (bB, nb, int(S), ops.beam_k(nb, len(eos or ())), len(beams) < 5 or bool(beams[4]))
+            K = self.beams[3]
+            self.eos = torch.tensor(list(eos), dtype=torch.int32, device=d) if eos else None
+            self.bscratch = ops.beam_scratch(bB, nb, K, d)
+            self.cand = (torch.zeros((bB * K,), dtype=torch.float32, device=d), torch.zeros((bB * K,), dtype=torch.int32, device=d),
+                         torch.zeros((bB * K,), dtype=torch.int32, device=d), torch.zeros((bB * K,), dtype=torch.uint8, device=d))
+            self.parent = torch.arange(B, dtype=torch.int32, device=d)
+            self.running = torch.zeros((B,), dtype=torch.float32, device=d)
+            self.kv_table = None
+            self._kv_table_gen = None
         self.use_graph = use_graph
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._gen = cache.generation
@@ -130,10 +153,30 @@ class DecodeSession:
             ops.gemv(self.x, ll.lm_head, out=self.logits)
         # greedy (or sampled) next token straight into the input slot of the next step (the V-padding columns of the
         # lm_head buffer are excluded through the row stride)
+        if self.beams is not None:
+            bB, nb, _S, K, tail = self.beams
+            ops.beam_candidates(self.logits[:, :ll.V], self.running, bB, nb, K, self.eos, self.bscratch, out=self.cand)
+            if tail:
+                self.beam_tail()
+            return
         if self.sample is None:
             ops.argmax(self.logits[:, :ll.V], out=self.tok)
         else:
             ops.argmax(self.logits[:, :ll.V], sampling=self.sample, ctr=self.pos, ctr_add=1, out=self.tok)
+        ops.incr_i32(self.pos, 1)
+
+    def _ensure_kv_table(self):
+        """The per-layer K / V pointer table of the reorder (raw pointers: rebuilt when the cache's storage moved)."""
+        if self.kv_table is None or self._kv_table_gen != self.cache.generation:
+            self.kv_table = ops.kv_beam_table(self.cache.k, self.cache.v, self.ll.device)
+            self._kv_table_gen = self.cache.generation
+
+    def beam_tail(self):
+        """The rest of a beam step behind the candidates: running beams from ``self.cand`` (its hit mask included), the KV
+        rows of the generated positions [S, pos + 1) follow their parents, pos += 1."""
+        bB, nb, S, _K, _tail = self.beams
+        ops.beam_select(*self.cand, bB, nb, tok=self.tok, parent=self.parent, running=self.running)
+        ops.kv_beam_reorder(self.kv_table, self.cache.k[0], self.parent, S, 1, pos_dev=self.pos)
         ops.incr_i32(self.pos, 1)
 
     def begin(self, first_token: Optional[torch.Tensor] = None):
@@ -144,6 +187,8 @@ class DecodeSession:
             self.tok.copy_(first_token.to(torch.int32).view(-1))
             if self.cache.key_valid is not None:
                 self.cache.key_valid[:, self.cache.seq_len:] = 1       # generated positions are always attended
+        if self.beams is not None:
+            self._ensure_kv_table()
         if self.use_graph and (self.graph is None or self._gen != self.cache.generation):
             self._capture()
 
@@ -154,12 +199,23 @@ class DecodeSession:
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         pos0, tok0 = self.pos.clone(), self.tok.clone()
+        beam0 = None
+        if self.beams is not None:                           # the warm-up step also moves the beams: restored with the rest
+            beam0 = [self.parent.clone(), self.running.clone()] + [t.clone() for t in self.cand]
+            S, hi = self.beams[2], self.cache.seq_len + 1
+            kv0 = [(t[:, :, S:hi].clone(), u[:, :, S:hi].clone()) for t, u in zip(self.cache.k, self.cache.v)]
         with torch.cuda.stream(s):
             self._enqueue_step()
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         self.pos.copy_(pos0)
         self.tok.copy_(tok0)
+        if beam0 is not None:
+            for t, t0 in zip([self.parent, self.running] + list(self.cand), beam0):
+                t.copy_(t0)
+            for (t, u), (t0, u0) in zip(zip(self.cache.k, self.cache.v), kv0):
+                t[:, :, S:hi].copy_(t0)
+                u[:, :, S:hi].copy_(u0)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             self._enqueue_step()
@@ -189,6 +245,8 @@ class DecodeSession:
                 raise ValueError("KV cache full") from None
             if self.cache.key_valid is not None and self.cache.key_valid.shape[1] != self.cache.ctx_max:
                 raise RuntimeError("key_valid out of step with the cache")
+            if self.beams is not None:
+                self._ensure_kv_table()
             if self.graph is not None and self._gen != self.cache.generation:
                 self._capture()
         if self.graph is not None:

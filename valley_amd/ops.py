@@ -1245,3 +1245,124 @@ def delta_finish(delta: torch.Tensor, mean: torch.Tensor, feats: torch.Tensor, B
     rc = _lib.load().vly_delta_finish(delta.data_ptr(), mean.data_ptr(), feats.data_ptr(), out.data_ptr(), B, T, H, _stream())
     _lib.check(rc, "vly_delta_finish")
     return out
+
+
+# ---- beam search (libvalley_hip_beam.so, include/valley_hip_beam.h) ---------------------------------------------------------
+BEAM_MAX_NB, BEAM_MAX_K = 16, 64
+
+
+def beam_k(nb: int, n_eos: int) -> int:
+    """Candidates kept per prompt and step: HF's beams_to_keep = max(2, 1 + n_eos) * nb."""
+    return max(2, 1 + n_eos) * nb
+
+
+def beam_scratch(B: int, nb: int, K: int, device) -> torch.Tensor:
+    """The zeroed device scratch of ``beam_candidates`` (its ticket counters are back at zero after every launch)."""
+    from . import lib_beam
+    n = int(lib_beam.load_beam().vly_beam_scratch_bytes(B, nb, K))
+    if n <= 0:
+        raise ValueError(f"beam_scratch: bad shape B={B} nb={nb} K={K}")
+    return torch.zeros(((n + 255) // 256 * 256,), dtype=torch.uint8, device=device)
+
+
+def beam_candidates(logits: torch.Tensor, running: torch.Tensor, B: int, nb: int, K: int, eos: Optional[torch.Tensor],
+                    scratch: torch.Tensor, out=None):
+    """logits fp32 [B * nb, V] (row stride may exceed V), running fp32 [B * nb] -> (score fp32, token int32, beam int32,
+    hit uint8), each [B * K]: per prompt the K best of log_softmax(row) + running over its nb * V continuations, best first,
+    ties to the lower flat index; ``beam`` is the absolute parent row, ``hit`` marks tokens in ``eos`` (int32, device)."""
+    from . import lib_beam
+    _chk(logits, torch.float32, "logits", contiguous=False)
+    _chk(running, torch.float32, "running")
+    _chk(scratch, torch.uint8, "scratch")
+    R, V = logits.shape
+    if logits.stride(1) != 1 or R != B * nb or running.numel() != R:
+        raise ValueError(f"beam_candidates: logits [{B} * {nb}, V] with unit column stride and running [{B * nb}] expected, got "
+                         f"{tuple(logits.shape)} / {tuple(running.shape)}")
+    n_eos = 0
+    if eos is not None:
+        _chk(eos, torch.int32, "eos")
+        n_eos = eos.numel()
+    need = int(lib_beam.load_beam().vly_beam_scratch_bytes(B, nb, K))
+    if scratch.numel() < need:
+        raise ValueError(f"beam_candidates: scratch holds {scratch.numel()} bytes, {need} needed")
+    if out is None:
+        d = logits.device
+        out = (torch.empty((B * K,), dtype=torch.float32, device=d), torch.empty((B * K,), dtype=torch.int32, device=d),
+               torch.empty((B * K,), dtype=torch.int32, device=d), torch.empty((B * K,), dtype=torch.uint8, device=d))
+    for t, dt, n in zip(out, (torch.float32, torch.int32, torch.int32, torch.uint8), ("score", "token", "beam", "hit")):
+        _chk(t, dt, n)
+        if t.numel() != B * K:
+            raise ValueError(f"beam_candidates: {n} must hold {B * K} values")
+    rc = lib_beam.load_beam().vly_beam_candidates(logits.data_ptr(), logits.stride(0), V, B, nb, running.data_ptr(), K,
+                                                  _ptr(eos) if n_eos else None, n_eos, scratch.data_ptr(),
+                                                  *[t.data_ptr() for t in out], _stream())
+    lib_beam.check(rc, "vly_beam_candidates")
+    return out
+
+
+def beam_select(score: torch.Tensor, token: torch.Tensor, beam: torch.Tensor, hit: torch.Tensor, B: int, nb: int,
+                tok=None, parent=None, running=None):
+    """Candidates [B * K] (+ hit mask uint8 [B * K]) -> (tok int32, parent int32, running fp32), each [B * nb]: per prompt the
+    nb best of score + hit * (-1e9), stable in candidate order (HF's running beams of the next step)."""
+    from . import lib_beam
+    n = score.numel()
+    for t, dt, name in ((score, torch.float32, "score"), (token, torch.int32, "token"), (beam, torch.int32, "beam"),
+                        (hit, torch.uint8, "hit")):
+        _chk(t, dt, name)
+        if t.numel() != n:
+            raise ValueError(f"beam_select: {name} must hold {n} values")
+    if n % B:
+        raise ValueError(f"beam_select: {n} candidates for {B} prompts")
+    K = n // B
+    d = score.device
+    tok = torch.empty((B * nb,), dtype=torch.int32, device=d) if tok is None else tok
+    parent = torch.empty((B * nb,), dtype=torch.int32, device=d) if parent is None else parent
+    running = torch.empty((B * nb,), dtype=torch.float32, device=d) if running is None else running
+    for t, dt, name in ((tok, torch.int32, "tok"), (parent, torch.int32, "parent"), (running, torch.float32, "running")):
+        _chk(t, dt, name)
+        if t.numel() != B * nb:
+            raise ValueError(f"beam_select: {name} must hold {B * nb} values")
+    rc = lib_beam.load_beam().vly_beam_select(score.data_ptr(), token.data_ptr(), beam.data_ptr(), hit.data_ptr(), B, nb, K,
+                                              tok.data_ptr(), parent.data_ptr(), running.data_ptr(), _stream())
+    lib_beam.check(rc, "vly_beam_select")
+    return tok, parent, running
+
+
+def kv_beam_table(kcaches, vcaches, device) -> torch.Tensor:
+    """int64 [L, 2] device table of the per-layer K and V cache base pointers ``kv_beam_reorder`` walks.  Holds raw pointers:
+    rebuild it whenever the cache's storage moves (``HipKVCache.generation`` changes)."""
+    rows, shape, dt = [], None, None
+    for k, v in zip(kcaches, vcaches):
+        for t, name in ((k, "kcache"), (v, "vcache")):
+            if not t.is_cuda or not t.is_contiguous() or t.dim() != 4 or t.shape[-1] != 128:
+                raise ValueError(f"kv_beam_table: {name} must be a contiguous device tensor [R, heads, ctx_max, 128]")
+            if t.element_size() not in (2, 4) or t.data_ptr() % 16:
+                raise ValueError(f"kv_beam_table: {name} must hold 2- or 4-byte elements on a 16-byte aligned base")
+            if shape is None:
+                shape, dt = tuple(t.shape), t.dtype
+            elif tuple(t.shape) != shape or t.dtype != dt:
+                raise ValueError("kv_beam_table: every cache of the table must have one shape and dtype")
+        rows.append([k.data_ptr(), v.data_ptr()])
+    if not rows:
+        raise ValueError("kv_beam_table: no layers")
+    return torch.tensor(rows, dtype=torch.int64).to(device)
+
+
+def kv_beam_reorder(table: torch.Tensor, kcache0: torch.Tensor, parent: torch.Tensor, lo: int, hi_add: int,
+                    pos_dev: Optional[torch.Tensor] = None) -> None:
+    """In place, every layer of ``table`` and both caches: row r <- row parent[r] over positions [lo, hi), hi = pos_dev[0] +
+    hi_add (read on the device) or hi_add without ``pos_dev``.  ``kcache0`` is one cache of the table (shape, element size)."""
+    from . import lib_beam
+    _chk(table, torch.int64, "table")
+    _chk(parent, torch.int32, "parent")
+    R, heads, ctx_max, hd = kcache0.shape
+    if table.dim() != 2 or table.shape[1] != 2 or hd != 128 or parent.numel() != R:
+        raise ValueError(f"kv_beam_reorder: table [L, 2], cache [R, heads, ctx_max, 128] and parent [R] expected, got "
+                         f"{tuple(table.shape)} / {tuple(kcache0.shape)} / {tuple(parent.shape)}")
+    pptr = None
+    if pos_dev is not None:
+        _chk(pos_dev, torch.int32, "pos_dev")
+        pptr = pos_dev.data_ptr()
+    rc = lib_beam.load_beam().vly_kv_beam_reorder(table.data_ptr(), table.shape[0], R, heads, ctx_max, kcache0.element_size(),
+                                                  parent.data_ptr(), int(lo), pptr, int(hi_add), _stream())
+    lib_beam.check(rc, "vly_kv_beam_reorder")

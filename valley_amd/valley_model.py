@@ -587,7 +587,8 @@ class ValleyLlamaForCausalLM:
     @torch.no_grad()
     def generate(self, input_ids, images=None, attention_mask=None, max_new_tokens: int = 64, do_sample: bool = False,
                  temperature: float = 1.0, stopping_criteria=None, eos_token_id=None, use_graph=True, top_k=None, top_p=None,
-                 seed=None, **kw):
+                 seed=None, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False,
+                 num_return_sequences: int = 1, return_dict_in_generate: bool = False, **kw):
         """Prefill + per-token KV decode (the loop of serve/model_worker.py:371-394; the reference's CLI
         path reaches the same through HF ``generate``, valley_model.py:432).  Greedy when not sampling or
         temperature < 1e-4, else temperature softmax + multinomial.  Decode steps run through a
@@ -597,7 +598,30 @@ class ValleyLlamaForCausalLM:
         Sampling with any of ``top_k`` / ``top_p`` / ``seed`` given draws every token on the device (ops.argmax with
         sampling parameters, inside the captured step): HF's temperature -> top-k -> top-p order, Gumbel-max with
         Philox noise.  ``seed`` is an int (row r uses seed + r) or a list of B ints; the same seed gives the same
-        sequence in graph, eager and generic-forward decoding.  Without a seed one is drawn from torch's generator."""
+        sequence in graph, eager and generic-forward decoding.  Without a seed one is drawn from torch's generator.
+
+        ``num_beams > 1``: HF's beam search (``length_penalty``, ``early_stopping`` True / False / "never",
+        ``num_return_sequences``); see ``_generate_beams``.  ``return_dict_in_generate``: an object with ``.sequences`` and
+        ``.sequences_scores`` (None without beams, as HF without output_scores)."""
+        if num_beams is None or int(num_beams) < 1:
+            raise ValueError(f"num_beams must be >= 1, got {num_beams!r}")
+        if int(num_beams) > 1:
+            if do_sample:
+                raise ValueError("beam sampling (num_beams > 1 with do_sample=True) is not supported")
+            if num_return_sequences > num_beams:
+                raise ValueError(f"num_return_sequences ({num_return_sequences}) must be <= num_beams ({num_beams})")
+            seq, scores = self._generate_beams(input_ids, images, attention_mask, max_new_tokens, int(num_beams), length_penalty,
+                                               early_stopping, int(num_return_sequences), stopping_criteria, eos_token_id,
+                                               use_graph, kw.get("pad_token_id", getattr(self.config, "pad_token_id", None)))
+            return SimpleNamespace(sequences=seq, sequences_scores=scores) if return_dict_in_generate else seq
+        if num_return_sequences != 1:
+            raise ValueError("num_return_sequences > 1 needs num_beams > 1 (sampling several sequences per prompt is not supported)")
+        seq = self._generate(input_ids, images, attention_mask, max_new_tokens, do_sample, temperature, stopping_criteria,
+                             eos_token_id, use_graph, top_k, top_p, seed, **kw)
+        return SimpleNamespace(sequences=seq, sequences_scores=None) if return_dict_in_generate else seq
+
+    def _generate(self, input_ids, images, attention_mask, max_new_tokens, do_sample, temperature, stopping_criteria, eos_token_id,
+                  use_graph, top_k, top_p, seed, **kw):
         input_ids = input_ids.to(self.device)
         B, S = input_ids.shape
         ctx = min(getattr(self.config, "max_position_embeddings", 2048), S + max_new_tokens)
@@ -672,6 +696,95 @@ class ValleyLlamaForCausalLM:
         if sess is not None:
             sess.check()                                     # ticket counters / grid-barrier abort word of the decode launches
         return seq
+
+    def _generate_beams(self, input_ids, images, attention_mask, max_new_tokens, nb, length_penalty, early_stopping, nrs,
+                        stopping_criteria, eos_token_id, use_graph, pad):
+        """Beam search (HF ``_beam_search``): the B prompts are prefilled once (images, padding mask) into rows [0, B) of a
+        B * nb-row cache, whose prompt positions the reorder kernel then copies into every beam row (key_valid likewise).
+        Every step picks the K best continuations per prompt on the device (ops.beam_candidates), selects the running beams
+        (ops.beam_select) and makes the KV rows of the generated positions follow their parents (ops.kv_beam_reorder); the
+        host keeps the hypotheses (valley_amd.beam) from one small copy of the candidates.  Up to 8 rows the step is the
+        decode session's (captured with ``use_graph=True``, eager with False); otherwise, or with ``use_graph=None``, it is
+        the generic forward followed by the same three kernels.  Stopping criteria are evaluated on the host over the
+        [B * K, cur_len + 1] candidate sequences, as HF does; they then hand the hit mask to the select kernel."""
+        from .beam import BeamSearch
+        from .decode import DecodeSession
+        from .llama import HipKVCache
+        input_ids = input_ids.to(self.device)
+        B, S = input_ids.shape
+        R, d = B * nb, self.device
+        ll = self.model.llama
+        eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id])
+        max_len = min(getattr(self.config, "max_position_embeddings", 2048), S + max_new_tokens)
+        if max_len <= S:
+            return input_ids.clone(), torch.zeros((B * nrs,), dtype=torch.float32)
+        state = BeamSearch(input_ids, nb, max_len, eos_ids=eos, pad_token_id=pad, length_penalty=length_penalty,
+                           early_stopping=early_stopping, num_return_sequences=nrs)
+        K = state.K
+        if state.K > ops.BEAM_MAX_K or nb > ops.BEAM_MAX_NB:
+            raise ValueError(f"beam search takes num_beams <= {ops.BEAM_MAX_NB} and max(2, 1 + n_eos) * num_beams <= "
+                             f"{ops.BEAM_MAX_K} (got {nb} beams, {len(eos)} EOS ids)")
+        cache = ll.new_cache(R, max_len + 1)
+        prompt = HipKVCache.rows_of(cache, 0, B)
+        out = self.forward(input_ids=input_ids, images=images, attention_mask=attention_mask, past_key_values=prompt,
+                           use_cache=True)
+        expand = torch.arange(R, dtype=torch.int32, device=d) // nb          # row b * nb + j <- prompt row b
+        table = ops.kv_beam_table(cache.k, cache.v, d)
+        ops.kv_beam_reorder(table, cache.k[0], expand, 0, S)
+        cache.seq_len = S
+        if prompt.key_valid is not None:
+            cache.key_valid = prompt.key_valid.index_select(0, expand.long()).contiguous()
+        eos_dev = torch.tensor(eos, dtype=torch.int32, device=d) if eos else None
+        scratch = ops.beam_scratch(B, nb, K, d)
+        running = state.initial_running().to(d)
+        first = out.logits[:, -1, :].float().repeat_interleave(nb, dim=0).contiguous()
+        cand = ops.beam_candidates(first, running, B, nb, K, eos_dev, scratch)
+        host_crit = stopping_criteria is not None and len(stopping_criteria) > 0
+        if self.model.precision == "fp32" or R > 8:
+            use_graph = None                                 # the GEMV decode session: 16-bit storage, <= 8 rows
+        sess = None
+        if use_graph is not None:
+            sess = DecodeSession(ll, cache, use_graph=bool(use_graph), beams=(B, nb, S, eos, not host_crit))
+
+        def finish_step(c):
+            """the host half of a step: hits (EOS, the caller's criteria), the host state; the hit mask goes back to the
+            device when a criterion added hits"""
+            seqs = state.candidates(c[0], c[1], c[2])
+            hits = c[3].to("cpu", torch.bool).view(-1)
+            added = False
+            for crit in (stopping_criteria if host_crit else ()):
+                r = crit(seqs.to(d), None)
+                new = r.to("cpu", torch.bool).view(-1) if isinstance(r, torch.Tensor) else torch.full_like(hits, bool(r))
+                added |= bool((new & ~hits).any())
+                hits = hits | new
+            state.advance(hits)
+            if added:
+                c[3].copy_(hits.to(torch.uint8).to(d))
+
+        finish_step(cand)
+        if sess is not None and not state.done:
+            ops.beam_select(*cand, B, nb, tok=sess.tok, parent=sess.parent, running=sess.running)
+            sess.begin(sess.tok.clone())                     # (the prompt rows are identical: nothing to reorder yet)
+        while not state.done:
+            if sess is not None:
+                sess.step()                                  # forward + candidates (+ select, reorder, pos += 1 without criteria)
+                finish_step(sess.cand)
+                if host_crit and not state.done:
+                    sess.beam_tail()
+            else:
+                tok, parent, running = ops.beam_select(*cand, B, nb, running=running)
+                if cache.seq_len > S:                        # the generated positions follow their parents
+                    ops.kv_beam_reorder(table, cache.k[0], parent, S, cache.seq_len)
+                if cache.seq_len + 1 > cache.ctx_max:
+                    break
+                out = self.forward(input_ids=tok.to(torch.long)[:, None], past_key_values=cache, use_cache=True)
+                cand = ops.beam_candidates(out.logits[:, -1, :], running, B, nb, K, eos_dev, scratch)
+                finish_step(cand)
+        torch.cuda.current_stream().synchronize()
+        if sess is not None:
+            sess.check()
+        seq, scores = state.result()
+        return seq.to(d), scores
 
     # -- tokenizer / prompt glue -----------------------------------------------------------------------
     def resize_token_embeddings(self, n: int):
@@ -761,7 +874,8 @@ class ValleyLlamaForCausalLM:
             images = video if isinstance(video, torch.Tensor) else load_video(video)
             images = images.permute(1, 0, 2, 3).unsqueeze(0)
         stopping = KeywordsStoppingCriteria(['###'], tokenizer, input_ids)
-        gk = {k: v for k, v in gen_kwargs.items() if k in ("max_new_tokens", "do_sample", "temperature", "eos_token_id")}
+        gk = {k: v for k, v in gen_kwargs.items() if k in ("max_new_tokens", "do_sample", "temperature", "eos_token_id", "num_beams",
+                                                            "length_penalty", "early_stopping")}
         output_ids = self.generate(input_ids=input_ids, images=images, stopping_criteria=[stopping], **gk)
         n_in = input_ids.shape[1]
         n_diff = (input_ids != output_ids[:, :n_in]).sum().item()
