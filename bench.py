@@ -20,8 +20,13 @@ One JSON line on rank 0.  `value` = frames pushed through the WHOLE path per sec
 ranks; `stages` gives the ViT-encode frames/s and prefill tokens/s measured with HIP events inside
 the same timed steps; `roofline` is for the dominant kernel (the MFMA GEMM instantiation with the
 largest share of time), achieved = algorithmic flop per launch / mean launch duration, both measured
-live with HIP events around every GEMM launch of the timed steps; `cpu_baseline` times the CPU oracle
-(oracle/valley_oracle.py, kind "port") on a bounded sample of the same workload on the host cores.
+live with HIP events around every GEMM launch of the timed steps.
+
+A plain run does only what that line needs: set up, warm up, time the steps, dump the outputs if asked, print.
+`--full` adds what takes runs or passes of its own: `roofline.traffic` / `mfma_busy` from rocprofv3 --pmc child
+passes, `cpu_baseline` (the CPU oracle, oracle/valley_oracle.py kind "port", on configs[0] on the host cores),
+`also` (the other BASELINE configurations and precisions, each a child run) and, at N > 1, the sharded-prefill form
+of the default configs[3] step.
 """
 from __future__ import annotations
 
@@ -361,7 +366,7 @@ def main():
                     help="default: c3 (BASELINE configs[2], the configuration the metric is quoted on) at --gpus 1; c4 = configs[3] at --gpus > 1")
     ap.add_argument("--prefill", default=None, choices=["sharded", "replicated"],
                     help="N > 1: 'replicated' (default) = configs[3] as written — every rank prefills all N x B sequences; 'sharded' = each rank "
-                         "prefills its own clips (weak scaling of the whole step; measured as well and attached under also.sharded_prefill)")
+                         "prefills its own clips (weak scaling of the whole step; with --full, measured as well and attached under also.sharded_prefill)")
     ap.add_argument("--simulate-ranks", type=int, default=1, metavar="R",
                     help="N = 1 only, with --prefill replicated: run THIS rank's share of an R-rank job — local clips encoded once, "
                          "their pooled tokens tiled R times in place of the all-gather, then the replicated prefill of all R x B "
@@ -375,16 +380,20 @@ def main():
                     help="run the batch as this many independent sub-batches on separate HIP streams (tail filling)")
     ap.add_argument("--pack-weights", type=int, default=int(os.environ.get("VALLEY_PACK_WEIGHTS", "1")), choices=[0, 1],
                     help="1 (default): the Llama prefill GEMMs read a second, block-ordered copy of the weights (ops.PackedWeight)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--traffic", default="live", choices=["live", "file", "none"],
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline line: live PMC traffic, the CPU baseline, the `also` workloads and, at N > 1, the "
+                         "sharded-prefill form of the default step (each off in a plain run)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--traffic", default=None, choices=["live", "file", "none"],
                     help="roofline.traffic of the dominant kernel: measured now by two rocprofv3 --pmc child passes (live, N=1 "
-                         "only), read from the newest profiles/**/r*_traffic_<config>.json (file), or null (none)")
+                         "only), read from the newest profiles/**/r*_traffic_<config>.json (file), or null (none); "
+                         "default: live with --full, none otherwise")
     ap.add_argument("--no-kernel-events", action="store_true", help="skip the per-launch HIP events (rocprof runs)")
     ap.add_argument("--also", default="auto",
                     help="extra workloads measured after the timed region, each in a child run of this script, and attached to the "
                          "line under `also` (N = 1 only): comma list of c2 (configs[1]), c4 (configs[3]'s per-GPU shape at N = 1), "
                          "decode (configs[4]: 13B, 256 tokens, hipGraph step), c3_fp16 (the headline workload on the fp16 library); "
-                         "'auto' = all four for the default c3 run, 'none' = off")
+                         "'auto' (default) = every workload of the ALSO table when c3 runs with --full, none otherwise; 'none' = off")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, tokens float64; rank 0's outputs; "
                          "a fixed sample of the logits and KV cache, at most 64 MB): same arguments, same inputs, so two builds compare "
@@ -392,6 +401,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.traffic is None:
+        args.traffic = "live" if args.full else "none"
     os.environ["VALLEY_PACK_WEIGHTS"] = str(args.pack_weights)      # read by the engines when they load their weights
 
     rank = int(os.environ.get("RANK", "0"))
@@ -411,7 +422,8 @@ def main():
         os.execv(sys.executable, cmd)
     if world != args.gpus:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}")
-    default_multi = world > 1 and args.prefill is None and args.config is None and not args.decode     # configs[3] as written + the sharded form
+    # --full at N > 1 on the default workload (configs[3] as written): also time the sharded form of the same step
+    sharded_form = args.full and world > 1 and args.prefill is None and args.config is None and not args.decode
     if args.config is None:
         args.config = "c3" if world == 1 else "c4"
     if args.prefill is None:
@@ -658,7 +670,7 @@ def main():
         elapsed = float(t.item())
 
     sharded_also = None
-    if default_multi:
+    if sharded_form:
         # the weak-scaling form of the same step (each rank prefills only its own B clips), timed the same way in the same processes
         ids_s = ids.repeat(B, 1)
         cache_s = mm.llama.new_cache(B, S)
@@ -804,12 +816,12 @@ def main():
                 "allgather_share_of_step": round(ag_ms / ms_step, 5),
                 "compare_with": "stages.vit_frames_per_s_per_gpu of the N = 1 line (same per-GPU workload: weak scaling)"})
         also = [] if (args.also == "none" or world > 1) else \
-            (list(ALSO) if args.config == "c3" else []) if args.also == "auto" else [a for a in args.also.split(",") if a]
+            (list(ALSO) if args.full and args.config == "c3" else []) if args.also == "auto" else [a for a in args.also.split(",") if a]
         also = [{"c4": "c4_n1", "decode": "c5_decode"}.get(a, a) for a in also]
         bad = [a for a in also if a not in ALSO]
         if bad:
             raise SystemExit(f"--also: unknown workload(s) {bad}; choose from c2, c4, decode, c3_fp16")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 result["cpu_baseline"] = cpu_baseline()
             except Exception as e:  # noqa: BLE001

@@ -1,7 +1,7 @@
 #!/bin/bash
 # The final artifacts of a round, from ONE GPU lease:  usage  gpurun -- 'bash tools/refresh_profiles.sh <tag>'   (e.g. v1)
 #   gpurun_out/final_<tag>/gpu_suite.txt            tail of `pytest tests -m gpu`
-#   .../bench_default.json                          the driver's command: python bench.py --steps 20 --warmup 5
+#   .../bench_default.json                          python bench.py --steps 20 --warmup 5 --full (the line with traffic, cpu_baseline, also)
 #   .../c3_kernel_stats.csv + bench_c3_under_rocprof.json     rocprofv3 --kernel-trace --stats of the c3 step
 #   .../decode_kernel_stats.csv                     the same for the hipGraph decode step
 #   .../pmc_*.txt                                   PMC counters of the dominant GEMMs (tools/pmc_gemm.sh), separate passes
@@ -14,7 +14,7 @@ if [ "${REFRESH_SKIP_TESTS:-0}" != 1 ]; then
   ( timeout 1200 python -m pytest tests -m gpu -q 2>&1 | tail -15 ) > $O/gpu_suite.txt 2>&1
   tail -3 $O/gpu_suite.txt
 fi
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python bench.py --steps 20 --warmup 5 --full > $O/bench_default.json 2> $O/bench_default.err
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c3 -o c3 -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --traffic none --also none > $O/bench_c3_under_rocprof.json 2>> $O/bench_default.err
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_decode -o dec -- python $R/bench.py --config c5 --decode 64 --warmup 4 --no-cpu-baseline --traffic none --also none > $O/bench_decode_under_rocprof.json 2>> $O/bench_default.err
