@@ -10,6 +10,7 @@ from valley_amd.runtime import HALF
 pytestmark = pytest.mark.gpu
 D = "cuda:0"
 EPI_SWIGLU = 2
+EPS = torch.finfo(HALF).eps      # one rounding of the 16-bit storage type: 2^-7 (bf16), 2^-10 (fp16)
 
 
 def rnd(shape, seed, scale=1.0):
@@ -38,7 +39,7 @@ def test_13b_gate_up_matches_hint_197_bit_for_bit(packed):
     rows = torch.tensor([0, 1, 191, 192, 1337, M - 1], device=D)
     y = a[rows].float() @ w.float().t()
     want = torch.nn.functional.silu(y[:, 0::2]) * y[:, 1::2]
-    assert float((got[rows].float() - want).norm() / want.norm()) < 4e-3
+    assert float((got[rows].float() - want).norm() / want.norm()) < 0.512 * EPS
 
 
 @pytest.mark.parametrize("M,N,K,packed", [

@@ -17,7 +17,9 @@
 //     28-31} of one chunk column: the 16 (row & 1, (row >> 1) & 7) pairs of either group are distinct);
 //   * bias goes in through the matrix cores: the first MFMA of a block is D = biasfrag . ones + 0, the bias split into three
 //     16-bit pieces at k = 0, 1, 2 (hi + lo + lo2 is the fp32 value exactly; products with 1.0 are exact) — no VALU add, no
-//     bias registers in the epilogue; it is loaded by one more LDS-DMA piece;
+//     bias registers in the epilogue; it is loaded by one more LDS-DMA piece.  bf16 storage only: three fp16 pieces are NOT the
+//     fp32 value (|b| >= 65520 overflows the first piece to inf, and bits below fp16's 2^-24 are lost), so libvalley_hip_f16.so adds
+//     the bias in fp32 in the epilogue instead (a 16-byte buffer load per 4 columns, out of range = 0), as gemm_p16.hip does;
 //   * the finished tile leaves through LDS: each wave turns a 32 x 128 block row around in its private 8 KB (ds_write_b64 of the
 //     packed lane-owned quads, ds_read_b128 of whole rows), so every store instruction writes 4 rows x 256 B (plain) or 8 rows x
 //     128 B (SwiGLU) — whole 128-byte lines — and the 16-byte pieces are PARKED in registers (32 x 4 = 128 VGPRs, the registers
@@ -140,6 +142,12 @@ gemm_p32_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ W, 
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(A), 0, (uint32_t)M * (uint32_t)lda * 2u, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<uint16_t*>(W), 0, ldw < 0 ? (uint32_t)((N + 63) >> 6) * 4096u * (uint32_t)nk * 2u : (uint32_t)N * (uint32_t)ldw * 2u, 0x00020000);
+#if VLY_FP16
+    // fp16 storage: the bias goes into the epilogue in fp32 (see the header); `bias` = null switches its pieces, reads and MFMAs off
+    const __amdgpu_buffer_rsrc_t rsE = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bias), 0, bias ? (uint32_t)N * 4u : 0u, 0x00020000);
+    const bool ebias = bias != nullptr;
+    bias = nullptr;
+#endif
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bias), 0, bias ? (uint32_t)N * 4u : 0u, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(Cv, 0, (uint32_t)M * (uint32_t)ldc * 2u, 0x00020000);
 
@@ -544,6 +552,18 @@ gemm_p32_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ W, 
                     __builtin_amdgcn_sched_barrier(0);
                     float v[16];
                     acc_read16(bi * 4 + bj, v);
+#if VLY_FP16
+                    if (ebias) {
+                        // v[4 q + i] is column 8 q + 4 h + i of the block: bias + the fp32 sum, before the activation
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const f32x4 b = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                                          rsE, (uint32_t)(en0 + wn0 + 32 * bj + 8 * q + 4 * h) * 4u, 0, 0));
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) v[4 * q + i] += b[i];
+                        }
+                    }
+#endif
                     if constexpr (SWI) {
                         // gate = even columns, up = odd: quad q gives outputs (8 q + 4 h) / 2 + {0, 1} of this block's 16
 #pragma unroll
