@@ -20,6 +20,11 @@ EXP_UNITS = ["decode_step.hip", "attention.hip", "gemm_bf16.hip", "gemv_bf16.hip
 # build serves the bf16 and fp16 libraries and the fp32 engine; the shipped libraries' exports stay exactly valley_hip.h's
 LIB_BEAM = os.path.join(LIBDIR, "libvalley_hip_beam.so")
 BEAM_SOURCES = ["beam.hip"]
+# the logits processors (include/valley_hip_logits.h): another companion of the same kind, fp32 logits and int32 ids only
+LIB_LOGITS = os.path.join(LIBDIR, "libvalley_hip_logits.so")
+LOGITS_SOURCES = ["logits.hip"]
+# the row top-K and merge that both companions compile (beam candidates over log-softmax and over processed scores)
+COMPANION_SHARED = ["beam_rows.inc"]
 SOURCES = ["capi.hip", "gemm_bf16.hip", "gemm_p32.hip", "gemm_p16.hip", "gemm_streamk.hip", "norm_elementwise.hip", "attention.hip", "temporal_delta.hip", "preprocess.hip", "gemv_bf16.hip", "precise_f32.hip", "gemm_skinny.hip", "decode_step.hip", "sampling.hip"]
 
 
@@ -35,8 +40,8 @@ def hipcc() -> str:
 
 def needs_build() -> bool:
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h)
-                                                                 for h in ("valley_hip.h", "valley_hip_beam.h")]
-    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, LIB_BEAM):
+                                                                 for h in ("valley_hip.h", "valley_hip_beam.h", "valley_hip_logits.h")]
+    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, LIB_BEAM, LIB_LOGITS):
         if not os.path.exists(lib):
             return True
         t = os.path.getmtime(lib)
@@ -52,6 +57,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(os.path.join(LIBDIR, "exp"), exist_ok=True)
     os.makedirs(os.path.join(LIBDIR, "exp_f16"), exist_ok=True)
     os.makedirs(os.path.join(LIBDIR, "beam"), exist_ok=True)
+    os.makedirs(os.path.join(LIBDIR, "logits"), exist_ok=True)
     if not force and not needs_build():
         return LIB
     variants = [(LIB, LIBDIR, [], SOURCES), (LIB_F16, os.path.join(LIBDIR, "f16"), ["-DVLY_FP16=1"], SOURCES),
@@ -79,15 +85,18 @@ def build(force: bool = False, verbose: bool = True) -> str:
             jobs.append((s, cmd))
             if s in AUDITED:
                 audits.append((s, odir, " ".join(flags) or "(default flags)"))
-    beam_dir = os.path.join(LIBDIR, "beam")
-    for s in BEAM_SOURCES:
-        o = os.path.join(beam_dir, s.replace(".hip", ".o"))
-        t_dep = max(os.path.getmtime(os.path.join(CSRC, s)), os.path.getmtime(os.path.abspath(__file__)),
-                    os.path.getmtime(os.path.join(HERE, "..", "include", "valley_hip_beam.h")))
-        if force or not os.path.exists(o) or os.path.getmtime(o) < t_dep:
-            jobs.append((s, [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-save-temps=obj", "-c",
-                             os.path.join(CSRC, s), "-o", o]))
-            audits.append((s, beam_dir, "(companion library)"))
+    companions = [(LIB_BEAM, "beam", BEAM_SOURCES, "valley_hip_beam.h"), (LIB_LOGITS, "logits", LOGITS_SOURCES, "valley_hip_logits.h")]
+    for _lib, sub, units, header in companions:
+        cdir = os.path.join(LIBDIR, sub)
+        for s in units:
+            o = os.path.join(cdir, s.replace(".hip", ".o"))
+            t_dep = max([os.path.getmtime(os.path.join(CSRC, s)), os.path.getmtime(os.path.abspath(__file__)),
+                         os.path.getmtime(os.path.join(HERE, "..", "include", header))] +
+                        [os.path.getmtime(os.path.join(CSRC, f)) for f in COMPANION_SHARED])
+            if force or not os.path.exists(o) or os.path.getmtime(o) < t_dep:
+                jobs.append((s, [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-save-temps=obj", "-c",
+                                 os.path.join(CSRC, s), "-o", o]))
+                audits.append((s, cdir, "(companion library)"))
     running = []
     while jobs or running:
         while jobs and len(running) < MAX_PARALLEL:
@@ -127,11 +136,12 @@ def build(force: bool = False, verbose: bool = True) -> str:
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
-    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_BEAM] + \
-        [os.path.join(LIBDIR, "beam", s.replace(".hip", ".o")) for s in BEAM_SOURCES]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
+    for lib, sub, units, _header in companions:
+        cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + \
+            [os.path.join(LIBDIR, sub, s.replace(".hip", ".o")) for s in units]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
     return LIB
 
 

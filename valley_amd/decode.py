@@ -12,7 +12,7 @@ lives on the device (``pos``) and is read by vly_rope_kv / vly_llama_attention t
 from __future__ import annotations
 
 import os
-from typing import Optional
+from typing import Optional, Sequence
 
 import torch
 
@@ -38,7 +38,8 @@ SPLIT_ROWS = os.environ.get("VALLEY_DECODE_SPLIT_ROWS", "1") != "0"       # roun
 
 class DecodeSession:
     def __init__(self, llama: HipLlama, cache: HipKVCache, use_graph: bool = True, per_row_positions: bool = False,
-                 sampling: bool = False, beams: Optional[tuple] = None):
+                 sampling: bool = False, beams: Optional[tuple] = None, processors: bool = False,
+                 processor_eos: Optional[Sequence[int]] = None):
         """``per_row_positions``: every batch row is an independent sequence at its own position (``pos`` is int32 [B]
         and advances by one per step for every row) — the captured step of valley_amd.serving.ContinuousBatcher.
         ``sampling``: the step draws each row's next token with that row's parameters in ``self.sample`` (int32 [B, 6],
@@ -50,7 +51,14 @@ class DecodeSession:
         scores in ``self.running`` (into ``self.cand``: score, token, parent row, hit — K per prompt) and then, with
         ``tail`` (default True: the hits are the EOS ids), the rest of the step: ops.beam_select into ``self.tok`` /
         ``self.parent`` / ``self.running``, ops.kv_beam_reorder of the generated positions [S, pos + 1) and pos += 1.
-        Without ``tail`` the caller writes its own hit mask into ``self.cand[3]`` and calls ``beam_tail()`` after each step."""
+        Without ``tail`` the caller writes its own hit mask into ``self.cand[3]`` and calls ``beam_tail()`` after each step.
+        ``processors``: HF's repetition penalty, no-repeat n-grams and minimum length run on the step's logits before the
+        argmax / draw (ops.logits_process), with each row's parameters in ``self.proc`` (int32 [B, 4], ops.processor_rows;
+        all rows neutral until written) over the token history ``self.hist`` (int32 [B, ctx_max]: the prompt ids, written by
+        ``begin(prompt_ids=...)`` or by the caller per slot, then every token fed to a step, appended on the device).  The
+        EOS ids of the minimum length are ``processor_eos`` (default: a beam session's EOS ids).  With beams the step runs
+        the history gather (rows follow their parents over [S, pos)), the processors on log_softmax(logits) and the
+        candidates over those scores (ops.logits_beam_candidates) instead of ops.beam_candidates."""
         self.ll, self.cache = llama, cache
         B, d = cache.batch, llama.device
         if B > 8:
@@ -95,6 +103,14 @@ class DecodeSession:
             self.running = torch.zeros((B,), dtype=torch.float32, device=d)
             self.kv_table = None
             self._kv_table_gen = None
+        self.proc = self.hist = self.proc_eos = None
+        if processors:
+            self.proc = ops.processor_rows([None] * B, device=d)
+            self.hist = torch.zeros((B, cache.ctx_max), dtype=torch.int32, device=d)
+            if processor_eos is None and beams is not None:
+                processor_eos = beams[3]
+            if processor_eos:
+                self.proc_eos = torch.tensor([int(e) for e in processor_eos], dtype=torch.int32, device=d)
         self.use_graph = use_graph
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._gen = cache.generation
@@ -154,11 +170,20 @@ class DecodeSession:
         # greedy (or sampled) next token straight into the input slot of the next step (the V-padding columns of the
         # lm_head buffer are excluded through the row stride)
         if self.beams is not None:
-            bB, nb, _S, K, tail = self.beams
-            ops.beam_candidates(self.logits[:, :ll.V], self.running, bB, nb, K, self.eos, self.bscratch, out=self.cand)
+            bB, nb, S, K, tail = self.beams
+            if self.proc is None:
+                ops.beam_candidates(self.logits[:, :ll.V], self.running, bB, nb, K, self.eos, self.bscratch, out=self.cand)
+            else:                                    # the history follows the last selection, then HF's processors on log-probs
+                ops.logits_history_gather(self.hist, self.parent, S, 0, len_dev=self.pos)
+                ops.logits_process(self.logits[:, :ll.V], self.proc, self.hist, self.pos, 1, tok=self.tok, eos=self.proc_eos,
+                                   log_softmax=True)
+                ops.logits_beam_candidates(self.logits[:, :ll.V], self.running, bB, nb, K, self.eos, self.bscratch,
+                                           out=self.cand)
             if tail:
                 self.beam_tail()
             return
+        if self.proc is not None:                    # the token fed to this step joins the history at index pos
+            ops.logits_process(self.logits[:, :ll.V], self.proc, self.hist, self.pos, 1, tok=self.tok, eos=self.proc_eos)
         if self.sample is None:
             ops.argmax(self.logits[:, :ll.V], out=self.tok)
         else:
@@ -179,9 +204,23 @@ class DecodeSession:
         ops.kv_beam_reorder(self.kv_table, self.cache.k[0], self.parent, S, 1, pos_dev=self.pos)
         ops.incr_i32(self.pos, 1)
 
-    def begin(self, first_token: Optional[torch.Tensor] = None):
+    def _ensure_hist(self):
+        """A processor session's history spans the cache's positions (it grows with a model-sized cache)."""
+        if self.hist is not None and self.hist.shape[1] < self.cache.ctx_max:
+            h = torch.zeros((self.B, self.cache.ctx_max), dtype=torch.int32, device=self.hist.device)
+            h[:, :self.hist.shape[1]].copy_(self.hist)
+            self.hist = h
+            self._gen = None                                 # a graph holds the old history's pointer: capture again
+
+    def begin(self, first_token: Optional[torch.Tensor] = None, prompt_ids: Optional[torch.Tensor] = None):
         """Call after the prefill filled ``cache``: sets the device position and the first input token (per-row sessions
-        manage ``pos`` / ``tok`` per slot themselves and call this once, to capture)."""
+        manage ``pos`` / ``tok`` per slot themselves and call this once, to capture).  ``prompt_ids`` [B, S]: the history
+        of a processor session (per-row sessions write ``self.hist`` per slot)."""
+        self._ensure_hist()
+        if prompt_ids is not None:
+            if self.hist is None:
+                raise ValueError("begin(prompt_ids=...) needs DecodeSession(..., processors=True)")
+            self.hist[:, :prompt_ids.shape[1]].copy_(prompt_ids.to(torch.int32))
         if not self.per_row:
             self.pos.fill_(self.cache.seq_len)
             self.tok.copy_(first_token.to(torch.int32).view(-1))
@@ -200,6 +239,7 @@ class DecodeSession:
         s.wait_stream(torch.cuda.current_stream())
         pos0, tok0 = self.pos.clone(), self.tok.clone()
         beam0 = None
+        hist0 = None if self.hist is None else self.hist.clone()   # the warm-up step appends / gathers: restored
         if self.beams is not None:                           # the warm-up step also moves the beams: restored with the rest
             beam0 = [self.parent.clone(), self.running.clone()] + [t.clone() for t in self.cand]
             S, hi = self.beams[2], self.cache.seq_len + 1
@@ -210,6 +250,8 @@ class DecodeSession:
         torch.cuda.synchronize()
         self.pos.copy_(pos0)
         self.tok.copy_(tok0)
+        if hist0 is not None:
+            self.hist.copy_(hist0)
         if beam0 is not None:
             for t, t0 in zip([self.parent, self.running] + list(self.cand), beam0):
                 t.copy_(t0)
@@ -247,6 +289,7 @@ class DecodeSession:
                 raise RuntimeError("key_valid out of step with the cache")
             if self.beams is not None:
                 self._ensure_kv_table()
+            self._ensure_hist()
             if self.graph is not None and self._gen != self.cache.generation:
                 self._capture()
         if self.graph is not None:

@@ -1366,3 +1366,153 @@ def kv_beam_reorder(table: torch.Tensor, kcache0: torch.Tensor, parent: torch.Te
     rc = lib_beam.load_beam().vly_kv_beam_reorder(table.data_ptr(), table.shape[0], R, heads, ctx_max, kcache0.element_size(),
                                                   parent.data_ptr(), int(lo), pptr, int(hi_add), _stream())
     lib_beam.check(rc, "vly_kv_beam_reorder")
+
+
+# ---- logits processors (libvalley_hip_logits.so, include/valley_hip_logits.h) -----------------------------------------------
+def processor_rows(repetition_penalty=None, no_repeat_ngram_size=None, min_length=None, min_new_tokens=None, prompt_len=0,
+                   device=None) -> torch.Tensor:
+    """Per-row parameters of ``logits_process`` as an int32 [M, 4] device tensor: repetition penalty (fp32 bits), no-repeat
+    n-gram size, absolute minimum length, 0.  Each argument is None (off), a scalar (broadcast) or a sequence of M values.
+    The minimum length of a row is max(min_length, prompt_len + min_new_tokens) (HF's MinLength and MinNewTokensLength
+    processors; they mask the EOS ids given to ``logits_process``).  Arguments are checked as transformers' processors
+    check them, with their messages."""
+    import numbers
+
+    def as_list(v):
+        if isinstance(v, torch.Tensor):
+            v = v.reshape(-1).tolist()
+        return list(v) if isinstance(v, (list, tuple)) else None
+
+    cols = {"penalty": repetition_penalty, "ngram": no_repeat_ngram_size, "min_length": min_length,
+            "min_new_tokens": min_new_tokens, "prompt_len": prompt_len}
+    lens = {len(as_list(c)) for c in cols.values() if as_list(c) is not None}
+    if len(lens) > 1:
+        raise ValueError(f"processor_rows: per-row arguments of different lengths {sorted(lens)}")
+    M = lens.pop() if lens else 1
+    if M < 1:
+        raise ValueError("processor_rows: no rows")
+    vals = {n: (as_list(c) if as_list(c) is not None else [c] * M) for n, c in cols.items()}
+    pen = []
+    for p in vals["penalty"]:
+        if p is None or (isinstance(p, numbers.Real) and not isinstance(p, bool) and p == 1.0):
+            pen.append(1.0)                                          # off (HF adds no processor for None or 1.0)
+            continue
+        if not isinstance(p, float) or not (p > 0):
+            raise ValueError(f"`penalty` has to be a strictly positive float, but is {p}")
+        pen.append(p)
+    ngram = []
+    for n in vals["ngram"]:
+        if n is None or (isinstance(n, numbers.Integral) and not isinstance(n, bool) and n == 0):
+            ngram.append(0)
+            continue
+        if not isinstance(n, int) or isinstance(n, bool) or n <= 0:
+            raise ValueError(f"`ngram_size` has to be a strictly positive integer, but is {n}")
+        ngram.append(min(n, 0x7fffffff))
+    mins = []
+    for ml, mn, pl in zip(vals["min_length"], vals["min_new_tokens"], vals["prompt_len"]):
+        if ml is not None and (not isinstance(ml, int) or isinstance(ml, bool) or ml < 0):
+            raise ValueError(f"`min_length` has to be a non-negative integer, but is {ml}")
+        if mn is not None and (not isinstance(mn, int) or isinstance(mn, bool) or mn < 0):
+            raise ValueError(f"`min_new_tokens` has to be a positive integer, but is {mn}")
+        if not isinstance(pl, int) or isinstance(pl, bool) or pl < 0:
+            raise ValueError(f"`prompt_length_to_skip` has to be a positive integer, but is {pl}")
+        m = ml or 0
+        if mn:
+            m = max(m, pl + mn)
+        mins.append(min(m, 0x7fffffff))
+    t = torch.zeros((M, 4), dtype=torch.int32)
+    t.view(torch.float32)[:, 0] = torch.tensor(pen, dtype=torch.float32)
+    t[:, 1] = torch.tensor(ngram, dtype=torch.int32)
+    t[:, 2] = torch.tensor(mins, dtype=torch.int32)
+    return t.to(device) if device is not None else t
+
+
+def logits_process(logits: torch.Tensor, params: torch.Tensor, hist: torch.Tensor, length: Optional[torch.Tensor] = None,
+                   len_add: int = 0, tok: Optional[torch.Tensor] = None, eos: Optional[torch.Tensor] = None,
+                   log_softmax: bool = False) -> torch.Tensor:
+    """In place on logits fp32 [R, V] (row stride may exceed V): HF's repetition penalty, no-repeat n-grams and minimum
+    length with the per-row ``params`` (int32 [R, 4], ``processor_rows``) over the history ``hist`` (int32 [R, hist_ld]).
+    Row r's length is ``length[r]`` (int32 [R]) or ``length[0]`` (int32 [1]), plus ``len_add``; with ``tok`` (int32 [R])
+    the kernel first writes tok[r] at position length - 1 of the history.  ``eos`` int32 [n] on the device.
+    ``log_softmax``: the row becomes x - logsumexp(x) first (beam search).  Everything is read on the device."""
+    from . import lib_logits
+    _chk(logits, torch.float32, "logits", contiguous=False)
+    _chk(params, torch.int32, "params")
+    _chk(hist, torch.int32, "hist")
+    R, V = logits.shape
+    if logits.stride(1) != 1 or tuple(params.shape) != (R, 4) or hist.dim() != 2 or hist.shape[0] != R:
+        raise ValueError(f"logits_process: logits [R, V] with unit column stride, params [R, 4] and hist [R, L] expected, got "
+                         f"{tuple(logits.shape)} / {tuple(params.shape)} / {tuple(hist.shape)}")
+    lptr, per_row = None, 0
+    if length is not None:
+        _chk(length, torch.int32, "length")
+        if length.numel() not in (1, R):
+            raise ValueError(f"logits_process: length must hold 1 or {R} values, got {length.numel()}")
+        lptr, per_row = length.data_ptr(), int(length.numel() == R and R > 1)
+    if tok is not None:
+        _chk(tok, torch.int32, "tok")
+        if tok.numel() != R:
+            raise ValueError(f"logits_process: tok must hold {R} values")
+    n_eos = 0
+    if eos is not None:
+        _chk(eos, torch.int32, "eos")
+        n_eos = eos.numel()
+    rc = lib_logits.load_logits().vly_logits_process(logits.data_ptr(), logits.stride(0), V, R, params.data_ptr(),
+                                                     hist.data_ptr(), hist.shape[1], lptr, per_row, int(len_add), _ptr(tok),
+                                                     _ptr(eos) if n_eos else None, n_eos, int(bool(log_softmax)), _stream())
+    lib_logits.check(rc, "vly_logits_process")
+    return logits
+
+
+def logits_history_gather(hist: torch.Tensor, parent: torch.Tensor, lo: int, hi_add: int,
+                          len_dev: Optional[torch.Tensor] = None) -> None:
+    """In place on hist int32 [R, hist_ld]: row r <- row parent[r] over positions [lo, hi), hi = len_dev[0] + hi_add (read on
+    the device) or hi_add without ``len_dev`` (beam search: a beam's history follows its parent, as its KV rows do)."""
+    from . import lib_logits
+    _chk(hist, torch.int32, "hist")
+    _chk(parent, torch.int32, "parent")
+    if hist.dim() != 2 or parent.numel() != hist.shape[0]:
+        raise ValueError(f"logits_history_gather: hist [R, L] and parent [R] expected, got {tuple(hist.shape)} / "
+                         f"{tuple(parent.shape)}")
+    lptr = None
+    if len_dev is not None:
+        _chk(len_dev, torch.int32, "len_dev")
+        lptr = len_dev.data_ptr()
+    rc = lib_logits.load_logits().vly_logits_history_gather(hist.data_ptr(), hist.shape[0], hist.shape[1], parent.data_ptr(),
+                                                            int(lo), lptr, int(hi_add), _stream())
+    lib_logits.check(rc, "vly_logits_history_gather")
+
+
+def logits_beam_candidates(scores: torch.Tensor, running: torch.Tensor, B: int, nb: int, K: int, eos: Optional[torch.Tensor],
+                           scratch: torch.Tensor, out=None):
+    """``beam_candidates`` over scores the caller processed (``logits_process(log_softmax=True)``): per prompt the K best of
+    scores + running, best first, ties to the lower flat index.  Same outputs and scratch as ``beam_candidates``."""
+    from . import lib_logits
+    _chk(scores, torch.float32, "scores", contiguous=False)
+    _chk(running, torch.float32, "running")
+    _chk(scratch, torch.uint8, "scratch")
+    R, V = scores.shape
+    if scores.stride(1) != 1 or R != B * nb or running.numel() != R:
+        raise ValueError(f"logits_beam_candidates: scores [{B} * {nb}, V] with unit column stride and running [{B * nb}] "
+                         f"expected, got {tuple(scores.shape)} / {tuple(running.shape)}")
+    n_eos = 0
+    if eos is not None:
+        _chk(eos, torch.int32, "eos")
+        n_eos = eos.numel()
+    h = lib_logits.load_logits()
+    need = int(h.vly_logits_beam_scratch_bytes(B, nb, K))
+    if scratch.numel() < need:
+        raise ValueError(f"logits_beam_candidates: scratch holds {scratch.numel()} bytes, {need} needed")
+    if out is None:
+        d = scores.device
+        out = (torch.empty((B * K,), dtype=torch.float32, device=d), torch.empty((B * K,), dtype=torch.int32, device=d),
+               torch.empty((B * K,), dtype=torch.int32, device=d), torch.empty((B * K,), dtype=torch.uint8, device=d))
+    for t, dt, n in zip(out, (torch.float32, torch.int32, torch.int32, torch.uint8), ("score", "token", "beam", "hit")):
+        _chk(t, dt, n)
+        if t.numel() != B * K:
+            raise ValueError(f"logits_beam_candidates: {n} must hold {B * K} values")
+    rc = h.vly_logits_beam_candidates(scores.data_ptr(), scores.stride(0), V, B, nb, running.data_ptr(), K,
+                                      _ptr(eos) if n_eos else None, n_eos, scratch.data_ptr(), *[t.data_ptr() for t in out],
+                                      _stream())
+    lib_logits.check(rc, "vly_logits_beam_candidates")
+    return out

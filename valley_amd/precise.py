@@ -157,6 +157,18 @@ class F32KVCache:
         self.key_valid: Optional[torch.Tensor] = None
         self.generation, self.growable, self.limit = 0, False, ctx_max
 
+    @classmethod
+    def rows_of(cls, parent: "F32KVCache", b0: int, b1: int) -> "F32KVCache":
+        """Same contract as llama.HipKVCache.rows_of: a cache over batch rows [b0, b1) of ``parent``, sharing its storage
+        (beam search prefills its prompts into the first rows of the beam cache this way)."""
+        c = cls.__new__(cls)
+        c.k = [t[b0:b1] for t in parent.k]
+        c.v = [t[b0:b1] for t in parent.v]
+        c.seq_len, c.ctx_max, c.batch = 0, parent.ctx_max, b1 - b0
+        c.key_valid = None if parent.key_valid is None else parent.key_valid[b0:b1]
+        c.generation, c.growable, c.limit = 0, False, parent.ctx_max
+        return c
+
     def reserve(self, n: int) -> None:
         """Same contract as llama.HipKVCache.reserve."""
         if n <= self.ctx_max:

@@ -109,10 +109,14 @@ class ContinuousBatcher:
     slots are fully independent sequences: ``vly_decode_attention_rows``.  Idle slots run along (their rows are computed
     and ignored: the GEMV cost does not depend on the row count), clamped inside their cache rows."""
 
-    def __init__(self, model, slots: int = 4, ctx_max: int = 1024, use_graph: bool = True, sampling: bool = False):
+    def __init__(self, model, slots: int = 4, ctx_max: int = 1024, use_graph: bool = True, sampling: bool = False,
+                 processors: bool = False, eos_token_id=None):
         """``sampling``: the captured step draws every slot's token with the parameters ``add`` gave its request
         (temperature, top-k, top-p, seed; DecodeSession ``sampling``) — a seeded request's tokens then depend on its seed
-        alone, not on its slot or its neighbours.  Greedy requests take the argmax in either kind of batcher."""
+        alone, not on its slot or its neighbours.  Greedy requests take the argmax in either kind of batcher.
+        ``processors``: the captured step runs HF's repetition penalty, no-repeat n-grams and minimum new tokens with the
+        parameters ``add`` gave each request (DecodeSession ``processors``), over the slot's history (its prompt, then its
+        tokens); ``eos_token_id`` (an int or a list) is what ``min_new_tokens`` keeps out."""
         if not 1 <= slots <= 8:
             raise ValueError("1 <= slots <= 8 (the decode step streams weights with the GEMV kernels)")
         self.model, self.ll = model, model.get_model().llama
@@ -124,7 +128,10 @@ class ContinuousBatcher:
         self.cache = self.ll.new_cache(slots, ctx_max)
         self.cache.key_valid = torch.ones((slots, ctx_max), dtype=torch.uint8, device=self.ll.device)
         self.sampling = sampling
-        self.sess = DecodeSession(self.ll, self.cache, use_graph=use_graph, per_row_positions=True, sampling=sampling)
+        self.processors = processors
+        eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id])
+        self.sess = DecodeSession(self.ll, self.cache, use_graph=use_graph, per_row_positions=True, sampling=sampling,
+                                  processors=processors, processor_eos=eos)
         self.live = [False] * slots
         self.length = [0] * slots                                # tokens in each slot's cache (host mirror of sess.pos)
         self._captured = False
@@ -133,11 +140,14 @@ class ContinuousBatcher:
         return [i for i, v in enumerate(self.live) if not v]
 
     def add(self, input_ids, images=None, attention_mask=None, first_token: Optional[int] = None, temperature: float = 0.0,
-            top_k: int = 0, top_p: float = 1.0, seed: Optional[int] = None) -> int:
+            top_k: int = 0, top_p: float = 1.0, seed: Optional[int] = None, repetition_penalty=None, no_repeat_ngram_size=None,
+            min_new_tokens=None) -> int:
         """Prefill one request (input_ids [1, S]) into a free slot; returns the slot.  The first generated token is the
         prefill's argmax unless ``first_token`` is given.  ``temperature`` >= 1e-4 (a sampling batcher only) makes the
         request sample: its first token is drawn on the device from the prefill's logits (draw counter S), the following
-        ones inside the captured step; without a ``seed`` one is drawn from torch's generator."""
+        ones inside the captured step; without a ``seed`` one is drawn from torch's generator.
+        ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_new_tokens`` (a processor batcher only) are HF's
+        processors for this request, applied to the prefill's logits (its first token) and inside every step."""
         if temperature > 0 and not self.sampling:
             raise ValueError("add(temperature > 0) needs ContinuousBatcher(..., sampling=True)")
         params = None
@@ -145,29 +155,43 @@ class ContinuousBatcher:
             if seed is None:
                 seed = int(torch.randint(0, 1 << 62, (1,)).item()) if temperature >= ops.GREEDY_T else 0
             params = ops.sampling_rows(float(temperature), top_k, top_p, seed, device=self.ll.device)   # validates
+        proc = None
+        wants = any(a is not None for a in (repetition_penalty, no_repeat_ngram_size, min_new_tokens))
+        if wants and not self.processors:
+            raise ValueError("add(repetition_penalty= / no_repeat_ngram_size= / min_new_tokens=) needs "
+                             "ContinuousBatcher(..., processors=True)")
+        ids = torch.as_tensor(input_ids, device=self.ll.device).view(1, -1)
+        S = ids.shape[1]
+        if self.processors:                                      # validates; a request without them gets a neutral row
+            proc = ops.processor_rows(repetition_penalty, no_repeat_ngram_size, None, min_new_tokens, prompt_len=S,
+                                      device=self.ll.device)
         free = self.free_slots()
         if not free:
             raise RuntimeError("no free slot")
         slot = free[0]
-        ids = torch.as_tensor(input_ids, device=self.ll.device).view(1, -1)
-        S = ids.shape[1]
         if S + 1 > self.ctx_max:
             raise ValueError("prompt does not fit the slot")
         self.cache.key_valid[slot] = 1
         row = type(self.cache).rows_of(self.cache, slot, slot + 1)
         out = self.model(input_ids=ids, images=images, attention_mask=attention_mask, past_key_values=row, use_cache=True)
+        last = out.logits[0, -1:]
+        if proc is not None:                                     # the slot's history: the prompt; the first token is processed
+            self.sess.proc[slot:slot + 1].copy_(proc)
+            self.sess.hist[slot, :S] = ids[0].to(torch.int32)
+            last = last.float().contiguous()
+            ops.logits_process(last, proc, self.sess.hist[slot:slot + 1], None, S, None, self.sess.proc_eos)
         if first_token is not None:
             tok = int(first_token)
         elif params is not None and temperature >= ops.GREEDY_T:
-            tok = int(ops.argmax(out.logits[0, -1:], sampling=params, ctr_add=S)[0])
+            tok = int(ops.argmax(last, sampling=params, ctr_add=S)[0])
         else:
-            tok = int(out.logits[0, -1].argmax())
+            tok = int(last[0].argmax())
         if params is not None:
             self.sess.sample[slot:slot + 1].copy_(params)
         self.sess.pos[slot:slot + 1].fill_(S)
         self.sess.tok[slot:slot + 1].fill_(tok)
         self.live[slot], self.length[slot] = True, S
-        self.last_prefill_logits = out.logits[0, -1]
+        self.last_prefill_logits = last[0]
         return slot
 
     def step(self) -> dict:

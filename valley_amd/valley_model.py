@@ -588,7 +588,8 @@ class ValleyLlamaForCausalLM:
     def generate(self, input_ids, images=None, attention_mask=None, max_new_tokens: int = 64, do_sample: bool = False,
                  temperature: float = 1.0, stopping_criteria=None, eos_token_id=None, use_graph=True, top_k=None, top_p=None,
                  seed=None, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False,
-                 num_return_sequences: int = 1, return_dict_in_generate: bool = False, **kw):
+                 num_return_sequences: int = 1, return_dict_in_generate: bool = False, repetition_penalty=None,
+                 no_repeat_ngram_size=None, min_length=None, min_new_tokens=None, **kw):
         """Prefill + per-token KV decode (the loop of serve/model_worker.py:371-394; the reference's CLI
         path reaches the same through HF ``generate``, valley_model.py:432).  Greedy when not sampling or
         temperature < 1e-4, else temperature softmax + multinomial.  Decode steps run through a
@@ -602,7 +603,15 @@ class ValleyLlamaForCausalLM:
 
         ``num_beams > 1``: HF's beam search (``length_penalty``, ``early_stopping`` True / False / "never",
         ``num_return_sequences``); see ``_generate_beams``.  ``return_dict_in_generate``: an object with ``.sequences`` and
-        ``.sequences_scores`` (None without beams, as HF without output_scores)."""
+        ``.sequences_scores`` (None without beams, as HF without output_scores).
+
+        ``repetition_penalty``, ``no_repeat_ngram_size``, ``min_length`` and ``min_new_tokens`` are HF's logits processors,
+        in HF's order before the sampling warpers, over every row's whole ``input_ids`` (prompt included) and the generated
+        tokens; with beams they see log_softmax(logits).  They run on the device (ops.logits_process), inside the captured
+        step too; the minimum lengths need ``eos_token_id``.  Greedy and sampling take them for any row count; beam search
+        takes them within its own limit (the KV reorder moves at most 128 rows of 16-bit or 64 rows of fp32 cache).  Left at
+        their defaults, nothing changes."""
+        proc = (repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens)
         if num_beams is None or int(num_beams) < 1:
             raise ValueError(f"num_beams must be >= 1, got {num_beams!r}")
         if int(num_beams) > 1:
@@ -612,16 +621,30 @@ class ValleyLlamaForCausalLM:
                 raise ValueError(f"num_return_sequences ({num_return_sequences}) must be <= num_beams ({num_beams})")
             seq, scores = self._generate_beams(input_ids, images, attention_mask, max_new_tokens, int(num_beams), length_penalty,
                                                early_stopping, int(num_return_sequences), stopping_criteria, eos_token_id,
-                                               use_graph, kw.get("pad_token_id", getattr(self.config, "pad_token_id", None)))
+                                               use_graph, kw.get("pad_token_id", getattr(self.config, "pad_token_id", None)), proc)
             return SimpleNamespace(sequences=seq, sequences_scores=scores) if return_dict_in_generate else seq
         if num_return_sequences != 1:
             raise ValueError("num_return_sequences > 1 needs num_beams > 1 (sampling several sequences per prompt is not supported)")
         seq = self._generate(input_ids, images, attention_mask, max_new_tokens, do_sample, temperature, stopping_criteria,
-                             eos_token_id, use_graph, top_k, top_p, seed, **kw)
+                             eos_token_id, use_graph, top_k, top_p, seed, proc=proc, **kw)
         return SimpleNamespace(sequences=seq, sequences_scores=None) if return_dict_in_generate else seq
 
+    @staticmethod
+    def _processor_table(proc, S: int, eos_ids, device) -> Optional[torch.Tensor]:
+        """HF's processors of ``generate`` as one row of ops.processor_rows (checked with HF's messages), or None when none
+        of them would act (HF adds no processor: the decode is exactly the one without them)."""
+        if proc is None or all(a is None for a in proc):
+            return None
+        rp, nr, ml, mn = proc
+        table = ops.processor_rows(rp, nr, ml, mn, prompt_len=S)
+        if not eos_ids:
+            table[:, 2] = 0                                  # HF's minimum lengths need an EOS id
+        if bool((table.view(torch.float32)[:, 0] == 1.0).all() and (table[:, 1] == 0).all() and (table[:, 2] <= S).all()):
+            return None
+        return table.to(device)
+
     def _generate(self, input_ids, images, attention_mask, max_new_tokens, do_sample, temperature, stopping_criteria, eos_token_id,
-                  use_graph, top_k, top_p, seed, **kw):
+                  use_graph, top_k, top_p, seed, proc=None, **kw):
         input_ids = input_ids.to(self.device)
         B, S = input_ids.shape
         ctx = min(getattr(self.config, "max_position_embeddings", 2048), S + max_new_tokens)
@@ -652,17 +675,30 @@ class ValleyLlamaForCausalLM:
         if pad is None:
             pad = int(eos[0]) if eos is not None else 0
         finished = torch.zeros((B,), dtype=torch.bool, device=self.device)     # HF: a finished row emits pad from then on
-        token = pick(out.logits[:, -1, :].contiguous(), S)
+        table = self._processor_table(proc, S, None if eos is None else eos.tolist(), self.device)
+        eos32 = hist = None
+        if table is not None:
+            table = table.expand(B, 4).contiguous()
+        last = out.logits[:, -1, :].contiguous()
+        if table is not None:                                # HF's processors over each row's whole input_ids, on the device
+            eos32 = None if eos is None else eos.to(torch.int32)
+            hist = torch.zeros((B, cache.ctx_max), dtype=torch.int32, device=self.device)
+            hist[:, :S] = input_ids.to(torch.int32)
+            ops.logits_process(last, table, hist, None, S, None, eos32)
+        token = pick(last, S)
         seq = torch.cat([input_ids, token[:, None]], dim=1)
         if B > 8 or self.model.precision == "fp32":
             use_graph = None                                 # the GEMV decode session is bf16, for <= 8 sequences
         sess = None
         if use_graph is not None:
             from .decode import DecodeSession
-            sess = DecodeSession(self.model.llama, cache, use_graph=bool(use_graph), sampling=sample is not None)
+            sess = DecodeSession(self.model.llama, cache, use_graph=bool(use_graph), sampling=sample is not None,
+                                 processors=table is not None, processor_eos=None if eos is None else eos.tolist())
             if sample is not None:
                 sess.sample.copy_(sample)
-            sess.begin(token)
+            if table is not None:
+                sess.proc.copy_(table)
+            sess.begin(token, prompt_ids=input_ids if table is not None else None)
         mask = attention_mask
         for _ in range(max_new_tokens - 1):
             if eos is not None:
@@ -688,7 +724,10 @@ class ValleyLlamaForCausalLM:
                 if mask is not None:
                     mask = torch.cat([mask.to(self.device), torch.ones((B, 1), dtype=mask.dtype, device=self.device)], dim=1)
                 out = self.forward(input_ids=token[:, None], attention_mask=mask, past_key_values=cache, use_cache=True)
-                token = torch.where(finished, torch.full_like(token, pad), pick(out.logits[:, -1, :].contiguous(), cache.seq_len))
+                last = out.logits[:, -1, :].contiguous()
+                if table is not None:                        # the fed token joins the history at index seq_len - 1
+                    ops.logits_process(last, table, hist, None, cache.seq_len, token.to(torch.int32), eos32)
+                token = torch.where(finished, torch.full_like(token, pad), pick(last, cache.seq_len))
             seq = torch.cat([seq, token[:, None]], dim=1)
         ops.sk_poll_async(self.device)
         torch.cuda.current_stream().synchronize()            # the caller decodes the tokens next; a stream-K hand-off
@@ -698,7 +737,7 @@ class ValleyLlamaForCausalLM:
         return seq
 
     def _generate_beams(self, input_ids, images, attention_mask, max_new_tokens, nb, length_penalty, early_stopping, nrs,
-                        stopping_criteria, eos_token_id, use_graph, pad):
+                        stopping_criteria, eos_token_id, use_graph, pad, proc=None):
         """Beam search (HF ``_beam_search``): the B prompts are prefilled once (images, padding mask) into rows [0, B) of a
         B * nb-row cache, whose prompt positions the reorder kernel then copies into every beam row (key_valid likewise).
         Every step picks the K best continuations per prompt on the device (ops.beam_candidates), selects the running beams
@@ -706,10 +745,11 @@ class ValleyLlamaForCausalLM:
         host keeps the hypotheses (valley_amd.beam) from one small copy of the candidates.  Up to 8 rows the step is the
         decode session's (captured with ``use_graph=True``, eager with False); otherwise, or with ``use_graph=None``, it is
         the generic forward followed by the same three kernels.  Stopping criteria are evaluated on the host over the
-        [B * K, cur_len + 1] candidate sequences, as HF does; they then hand the hit mask to the select kernel."""
+        [B * K, cur_len + 1] candidate sequences, as HF does; they then hand the hit mask to the select kernel.
+        With processors (``proc``) every beam row keeps its token history on the device (following its parent, as its KV
+        rows do), HF's processors run on log_softmax(logits) and the candidates are taken over those scores."""
         from .beam import BeamSearch
         from .decode import DecodeSession
-        from .llama import HipKVCache
         input_ids = input_ids.to(self.device)
         B, S = input_ids.shape
         R, d = B * nb, self.device
@@ -725,12 +765,12 @@ class ValleyLlamaForCausalLM:
             raise ValueError(f"beam search takes num_beams <= {ops.BEAM_MAX_NB} and max(2, 1 + n_eos) * num_beams <= "
                              f"{ops.BEAM_MAX_K} (got {nb} beams, {len(eos)} EOS ids)")
         cache = ll.new_cache(R, max_len + 1)
-        prompt = HipKVCache.rows_of(cache, 0, B)
+        prompt = type(cache).rows_of(cache, 0, B)            # (HipKVCache, or the fp32 engine's F32KVCache)
         out = self.forward(input_ids=input_ids, images=images, attention_mask=attention_mask, past_key_values=prompt,
                            use_cache=True)
         expand = torch.arange(R, dtype=torch.int32, device=d) // nb          # row b * nb + j <- prompt row b
-        table = ops.kv_beam_table(cache.k, cache.v, d)
-        ops.kv_beam_reorder(table, cache.k[0], expand, 0, S)
+        kv_table = ops.kv_beam_table(cache.k, cache.v, d)
+        ops.kv_beam_reorder(kv_table, cache.k[0], expand, 0, S)
         cache.seq_len = S
         if prompt.key_valid is not None:
             cache.key_valid = prompt.key_valid.index_select(0, expand.long()).contiguous()
@@ -738,13 +778,25 @@ class ValleyLlamaForCausalLM:
         scratch = ops.beam_scratch(B, nb, K, d)
         running = state.initial_running().to(d)
         first = out.logits[:, -1, :].float().repeat_interleave(nb, dim=0).contiguous()
-        cand = ops.beam_candidates(first, running, B, nb, K, eos_dev, scratch)
+        table = self._processor_table(proc, S, eos, d)
+        hist = None
+        if table is None:
+            cand = ops.beam_candidates(first, running, B, nb, K, eos_dev, scratch)
+        else:                                                # HF: processors over log_softmax(logits), then + running
+            table = table.expand(R, 4).contiguous()
+            hist = torch.zeros((R, cache.ctx_max), dtype=torch.int32, device=d)
+            hist[:, :S] = input_ids.to(torch.int32).repeat_interleave(nb, dim=0)
+            ops.logits_process(first, table, hist, None, S, None, eos_dev, log_softmax=True)
+            cand = ops.logits_beam_candidates(first, running, B, nb, K, eos_dev, scratch)
         host_crit = stopping_criteria is not None and len(stopping_criteria) > 0
         if self.model.precision == "fp32" or R > 8:
             use_graph = None                                 # the GEMV decode session: 16-bit storage, <= 8 rows
         sess = None
         if use_graph is not None:
-            sess = DecodeSession(ll, cache, use_graph=bool(use_graph), beams=(B, nb, S, eos, not host_crit))
+            sess = DecodeSession(ll, cache, use_graph=bool(use_graph), beams=(B, nb, S, eos, not host_crit),
+                                 processors=table is not None)
+            if table is not None:
+                sess.proc.copy_(table)
 
         def finish_step(c):
             """the host half of a step: hits (EOS, the caller's criteria), the host state; the hit mask goes back to the
@@ -764,7 +816,7 @@ class ValleyLlamaForCausalLM:
         finish_step(cand)
         if sess is not None and not state.done:
             ops.beam_select(*cand, B, nb, tok=sess.tok, parent=sess.parent, running=sess.running)
-            sess.begin(sess.tok.clone())                     # (the prompt rows are identical: nothing to reorder yet)
+            sess.begin(sess.tok.clone(), prompt_ids=hist[:, :S] if hist is not None else None)   # (nothing to reorder yet)
         while not state.done:
             if sess is not None:
                 sess.step()                                  # forward + candidates (+ select, reorder, pos += 1 without criteria)
@@ -774,11 +826,18 @@ class ValleyLlamaForCausalLM:
             else:
                 tok, parent, running = ops.beam_select(*cand, B, nb, running=running)
                 if cache.seq_len > S:                        # the generated positions follow their parents
-                    ops.kv_beam_reorder(table, cache.k[0], parent, S, cache.seq_len)
+                    ops.kv_beam_reorder(kv_table, cache.k[0], parent, S, cache.seq_len)
+                    if hist is not None:
+                        ops.logits_history_gather(hist, parent, S, cache.seq_len)
                 if cache.seq_len + 1 > cache.ctx_max:
                     break
                 out = self.forward(input_ids=tok.to(torch.long)[:, None], past_key_values=cache, use_cache=True)
-                cand = ops.beam_candidates(out.logits[:, -1, :], running, B, nb, K, eos_dev, scratch)
+                if hist is None:
+                    cand = ops.beam_candidates(out.logits[:, -1, :], running, B, nb, K, eos_dev, scratch)
+                else:
+                    x = out.logits[:, -1, :]
+                    ops.logits_process(x, table, hist, None, cache.seq_len, tok, eos_dev, log_softmax=True)
+                    cand = ops.logits_beam_candidates(x, running, B, nb, K, eos_dev, scratch)
                 finish_step(cand)
         torch.cuda.current_stream().synchronize()
         if sess is not None:
@@ -875,7 +934,8 @@ class ValleyLlamaForCausalLM:
             images = images.permute(1, 0, 2, 3).unsqueeze(0)
         stopping = KeywordsStoppingCriteria(['###'], tokenizer, input_ids)
         gk = {k: v for k, v in gen_kwargs.items() if k in ("max_new_tokens", "do_sample", "temperature", "eos_token_id", "num_beams",
-                                                            "length_penalty", "early_stopping")}
+                                                            "length_penalty", "early_stopping", "repetition_penalty",
+                                                            "no_repeat_ngram_size", "min_length", "min_new_tokens")}
         output_ids = self.generate(input_ids=input_ids, images=images, stopping_criteria=[stopping], **gk)
         n_in = input_ids.shape[1]
         n_diff = (input_ids != output_ids[:, :n_in]).sum().item()
