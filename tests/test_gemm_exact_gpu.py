@@ -16,6 +16,7 @@ import os
 import pytest
 import torch
 
+from tests.row_oracle import SENTINEL, assert_guards, guarded as _guarded      # (the guards live with the row oracle now)
 from valley_amd import ops as _ops
 from valley_amd.runtime import HALF  # the library's 16-bit storage type: bf16, or fp16 under VALLEY_PRECISION=fp16
 
@@ -23,7 +24,6 @@ pytestmark = pytest.mark.gpu
 D = "cuda:0"
 FP16 = HALF == torch.float16
 EXACT_LIMIT = 2.0 ** 21          # 2^24 * 2^-3: below it every multiple of 2^-3 is an fp32 number
-SENTINEL = 7.0
 
 # exact results at the 16-bit type's rounding ties and overflow edge (as final outputs: bias and residual are taken out of the product)
 if FP16:
@@ -114,18 +114,7 @@ def assert_exact(got, truth, what):
 
 
 def guarded(M, No, dtype, rows=3, cols=None):
-    """An output view [M, No] inside a sentinel-filled buffer with guard rows below and guard columns to the right (16-bit rows
-    stay 16-byte aligned)."""
-    if cols is None:
-        cols = (8 - No % 8) % 8 + 8 if dtype != torch.float32 else 4
-    buf = torch.full((M + rows, No + cols), SENTINEL, dtype=dtype, device=D)
-    return buf, buf[:M, :No]
-
-
-def assert_guards(buf, M, No, what):
-    outside = torch.ones(buf.shape, dtype=torch.bool, device=buf.device)
-    outside[:M, :No] = False
-    assert bool((buf[outside] == SENTINEL).all()), f"{what}: a guard row or column was written"
+    return _guarded(M, No, dtype, rows, cols, device=D)
 
 
 @functools.lru_cache(maxsize=16)
