@@ -23,6 +23,10 @@ BEAM_SOURCES = ["beam.hip"]
 # the logits processors (include/valley_hip_logits.h): another companion of the same kind, fp32 logits and int32 ids only
 LIB_LOGITS = os.path.join(LIBDIR, "libvalley_hip_logits.so")
 LOGITS_SOURCES = ["logits.hip"]
+# weight-only INT8 decode (include/valley_hip_wq.h): the quantizer and the int8 weight-streaming GEMVs; one build serves both
+# 16-bit storage types (every compute entry takes the dtype code), so the main libraries' exports stay exactly valley_hip.h's
+LIB_WQ = os.path.join(LIBDIR, "libvalley_hip_wq.so")
+WQ_SOURCES = ["wq.hip"]
 # the row top-K and merge that both companions compile (beam candidates over log-softmax and over processed scores)
 COMPANION_SHARED = ["beam_rows.inc"]
 SOURCES = ["capi.hip", "gemm_bf16.hip", "gemm_p32.hip", "gemm_p16.hip", "gemm_streamk.hip", "norm_elementwise.hip", "attention.hip", "temporal_delta.hip", "preprocess.hip", "gemv_bf16.hip", "precise_f32.hip", "gemm_skinny.hip", "decode_step.hip", "sampling.hip"]
@@ -40,8 +44,8 @@ def hipcc() -> str:
 
 def needs_build() -> bool:
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h)
-                                                                 for h in ("valley_hip.h", "valley_hip_beam.h", "valley_hip_logits.h")]
-    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, LIB_BEAM, LIB_LOGITS):
+                                                                 for h in ("valley_hip.h", "valley_hip_beam.h", "valley_hip_logits.h", "valley_hip_wq.h")]
+    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, LIB_BEAM, LIB_LOGITS, LIB_WQ):
         if not os.path.exists(lib):
             return True
         t = os.path.getmtime(lib)
@@ -58,6 +62,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(os.path.join(LIBDIR, "exp_f16"), exist_ok=True)
     os.makedirs(os.path.join(LIBDIR, "beam"), exist_ok=True)
     os.makedirs(os.path.join(LIBDIR, "logits"), exist_ok=True)
+    os.makedirs(os.path.join(LIBDIR, "wq"), exist_ok=True)
     if not force and not needs_build():
         return LIB
     variants = [(LIB, LIBDIR, [], SOURCES), (LIB_F16, os.path.join(LIBDIR, "f16"), ["-DVLY_FP16=1"], SOURCES),
@@ -85,14 +90,15 @@ def build(force: bool = False, verbose: bool = True) -> str:
             jobs.append((s, cmd))
             if s in AUDITED:
                 audits.append((s, odir, " ".join(flags) or "(default flags)"))
-    companions = [(LIB_BEAM, "beam", BEAM_SOURCES, "valley_hip_beam.h"), (LIB_LOGITS, "logits", LOGITS_SOURCES, "valley_hip_logits.h")]
+    companions = [(LIB_BEAM, "beam", BEAM_SOURCES, "valley_hip_beam.h"), (LIB_LOGITS, "logits", LOGITS_SOURCES, "valley_hip_logits.h"),
+                  (LIB_WQ, "wq", WQ_SOURCES, "valley_hip_wq.h")]
     for _lib, sub, units, header in companions:
         cdir = os.path.join(LIBDIR, sub)
         for s in units:
             o = os.path.join(cdir, s.replace(".hip", ".o"))
             t_dep = max([os.path.getmtime(os.path.join(CSRC, s)), os.path.getmtime(os.path.abspath(__file__)),
                          os.path.getmtime(os.path.join(HERE, "..", "include", header))] +
-                        [os.path.getmtime(os.path.join(CSRC, f)) for f in COMPANION_SHARED])
+                        [os.path.getmtime(os.path.join(CSRC, f)) for f in (["common.hpp"] if sub == "wq" else COMPANION_SHARED)])
             if force or not os.path.exists(o) or os.path.getmtime(o) < t_dep:
                 jobs.append((s, [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-save-temps=obj", "-c",
                                  os.path.join(CSRC, s), "-o", o]))

@@ -81,8 +81,8 @@ def load_lora(path: str, device):
     return model, tokenizer
 
 
-def load(model_name: str):
-    """-> (model on the GPU in eval mode with its token ids bound, tokenizer)."""
+def load(model_name: str, weight_quant: Optional[str] = None):
+    """-> (model on the GPU in eval mode with its token ids bound, tokenizer).  ``weight_quant="int8"``: int8 decode weights."""
     path = os.path.expanduser(model_name)
     device = _require_gpu()
     if "lora" in path:
@@ -90,7 +90,9 @@ def load(model_name: str):
     else:
         from transformers import AutoTokenizer
         tokenizer = AutoTokenizer.from_pretrained(path)
-        model = ValleyLlamaForCausalLM.from_pretrained(path, torch_dtype=entry_dtype())
+        model = ValleyLlamaForCausalLM.from_pretrained(path, torch_dtype=entry_dtype(), weight_quant=weight_quant)
+    if weight_quant and "lora" in path:
+        model.quantize_decode_weights(weight_quant)
     init_vision_token(model, tokenizer)
     return model.to(device).eval(), tokenizer
 
@@ -98,7 +100,7 @@ def load(model_name: str):
 def main(args) -> str:
     """One video, one question, one printed answer.  ``args`` carries model_name, query, video_file, system_prompt
     (and vision_tower, unused: the tower comes with the checkpoint)."""
-    model, tokenizer = load(args.model_name)
+    model, tokenizer = load(args.model_name, getattr(args, "weight_quant", None))
     turns = [{"role": "system", "content": args.system_prompt or SYSTEM_TURN}, {"role": "user", "content": args.query}]
     answer = model.completion(tokenizer, args.video_file, turns, dict(GREEDY), _require_gpu())
     print(answer)
@@ -113,6 +115,8 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
                           ("--vision-tower", None),
                           ("--system-prompt", "")):
         ap.add_argument(flag, type=str, default=default)
+    ap.add_argument("--weight-quant", type=str, default=None, choices=["int8"],
+                    help="decode with int8 projection weights (weight-only quantization; prefill stays 16-bit)")
     return ap.parse_args(argv)
 
 

@@ -64,6 +64,10 @@ class DecodeSession:
         if B > 8:
             raise ValueError("decode sessions stream weights with the GEMV kernel: batch <= 8")
         self.B = B
+        self.wq = bool(getattr(llama, "weight_quant", None))     # the four projections of every layer stream int8 weights
+        if self.wq and (PERSISTENT or MERGE_IN == "oproj"):
+            raise ValueError("an int8-quantized engine decodes with the per-layer launches only: unset VALLEY_DECODE_PERSISTENT and "
+                             "VALLEY_DECODE_MERGE=oproj (those forms read 16-bit weights)")
         self.per_row = per_row_positions
         self.tok = torch.zeros((B,), dtype=torch.int32, device=d)          # token fed to the next step
         self.pos = torch.zeros((B if per_row_positions else 1,), dtype=torch.int32, device=d)   # on the device: replays need no patching
@@ -121,6 +125,7 @@ class DecodeSession:
         # the three norm -> projection seams as one launch each where the fused kernel takes the shape (bit-identical either way;
         # VALLEY_DECODE_FUSE_NORM=0 keeps the pairs, for A/B runs)
         fused = FUSE_NORM and ops.gemv_rmsnorm_ok(B, ll.H)
+        wq, wq_fused = self.wq, self.wq and fused and ops.wq_gemv_rmsnorm_ok(B, ll.H)
         # every head over four workgroups.  Merged inside the attention launch (the default) it does not depend on the o GEMV's form, so
         # three to eight rows take it too: at eight requests decode_fused_kernel's 320 workgroups of 512 threads are 1.25 rounds of one
         # workgroup per CU (23 us per layer, 15 % of the step); 1280 quarter-head workgroups stream the same K / V evenly
@@ -135,7 +140,12 @@ class DecodeSession:
                               self.per_row, ll.heads, ll.I, ll.eps, c.ctx_max, self.sync)
         for li in range(0 if self.persistent else ll.L):
             L = ll.layers[li]
-            if fused:
+            if wq_fused:
+                ops.wq_gemv_rmsnorm(self.h, L["ln1"], ll.eps, *L["wq_qkv"], out=self.qkv)
+            elif wq:
+                ops.rmsnorm(self.h, L["ln1"], ll.eps, out=self.x)
+                ops.wq_gemv(self.x, *L["wq_qkv"], out=self.qkv)
+            elif fused:
                 ops.gemv_rmsnorm(self.h, L["ln1"], ll.eps, L["w_qkv"], out=self.qkv)      # input_layernorm inside the q|k|v GEMV
             else:
                 ops.rmsnorm(self.h, L["ln1"], ll.eps, out=self.x)
@@ -144,7 +154,7 @@ class DecodeSession:
                 if MERGE_IN == "attn":
                     ops.decode_attention_split(self.qkv, c.k[li], c.v[li], ll.cos, ll.sin, c.key_valid, B, ll.heads, 0, self.partials,
                                                past_dev=self.pos, per_row=self.per_row, out=self.att, arrivals=self.arrivals)
-                    ops.gemv(self.att, L["w_o"], residual=self.h, out=self.h)
+                    self._o_proj(L)
                 else:
                     ops.decode_attention_split(self.qkv, c.k[li], c.v[li], ll.cos, ll.sin, c.key_valid, B, ll.heads, 0,
                                                self.partials, past_dev=self.pos, per_row=self.per_row)
@@ -155,13 +165,21 @@ class DecodeSession:
                 ops.decode_attention(self.qkv, c.k[li], c.v[li], ll.cos, ll.sin, c.key_valid, B, ll.heads, 0, out=self.att,
                                      past_dev=self.pos)          # RoPE + KV append + attention in one launch
             if not split:
-                ops.gemv(self.att, L["w_o"], residual=self.h, out=self.h)
-            if fused:
+                self._o_proj(L)
+            if wq_fused:
+                ops.wq_gemv_rmsnorm(self.h, L["ln2"], ll.eps, *L["wq_gu"], epilogue=ops.EPI_SWIGLU, out=self.mlp)
+            elif wq:
+                ops.rmsnorm(self.h, L["ln2"], ll.eps, out=self.x)
+                ops.wq_gemv(self.x, *L["wq_gu"], epilogue=ops.EPI_SWIGLU, out=self.mlp)
+            elif fused:
                 ops.gemv_rmsnorm(self.h, L["ln2"], ll.eps, L["w_gu"], epilogue=ops.EPI_SWIGLU, out=self.mlp)
             else:
                 ops.rmsnorm(self.h, L["ln2"], ll.eps, out=self.x)
                 ops.gemv(self.x, L["w_gu"], epilogue=ops.EPI_SWIGLU, out=self.mlp)
-            ops.gemv(self.mlp, L["w_down"], residual=self.h, out=self.h)
+            if wq:
+                ops.wq_gemv(self.mlp, *L["wq_down"], residual=self.h, out=self.h)
+            else:
+                ops.gemv(self.mlp, L["w_down"], residual=self.h, out=self.h)
         if fused:
             ops.gemv_rmsnorm(self.h, ll.norm, ll.eps, ll.lm_head, out=self.logits)
         else:
@@ -189,6 +207,12 @@ class DecodeSession:
         else:
             ops.argmax(self.logits[:, :ll.V], sampling=self.sample, ctr=self.pos, ctr_add=1, out=self.tok)
         ops.incr_i32(self.pos, 1)
+
+    def _o_proj(self, L):
+        if self.wq:
+            ops.wq_gemv(self.att, *L["wq_o"], residual=self.h, out=self.h)
+        else:
+            ops.gemv(self.att, L["w_o"], residual=self.h, out=self.h)
 
     def _ensure_kv_table(self):
         """The per-layer K / V pointer table of the reorder (raw pointers: rebuilt when the cache's storage moved)."""

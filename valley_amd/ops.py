@@ -1516,3 +1516,79 @@ def logits_beam_candidates(scores: torch.Tensor, running: torch.Tensor, B: int, 
                                       _stream())
     lib_logits.check(rc, "vly_logits_beam_candidates")
     return out
+
+
+# ---- weight-only INT8 decode (libvalley_hip_wq.so, include/valley_hip_wq.h) ------------------------------------------------
+def _wq_dtype() -> int:
+    return 1 if runtime.HALF == torch.float16 else 0          # the codes of vly_storage_dtype
+
+
+def wq_quantize(w: torch.Tensor):
+    """Per-row symmetric int8 quantization of a 16-bit weight [N, K]: -> (q int8 [N, K], scale fp32 [N]) with
+    s = amax / 127, q = clamp(rint(w / s), -127, 127); an all-zero row gives s = 1, q = 0."""
+    from . import lib_wq
+    _chk(w, runtime.HALF, "w", contiguous=False)
+    if w.dim() != 2 or w.stride(1) != 1:
+        raise ValueError(f"wq_quantize: a [N, K] weight with unit column stride expected, got {tuple(w.shape)}")
+    N, K = w.shape
+    q = torch.empty((N, K), dtype=torch.int8, device=w.device)
+    scale = torch.empty((N,), dtype=torch.float32, device=w.device)
+    rc = lib_wq.load_wq().vly_wq_quantize_rows(w.data_ptr(), w.stride(0), N, K, _wq_dtype(), q.data_ptr(), scale.data_ptr(), _stream())
+    lib_wq.check(rc, "vly_wq_quantize_rows")
+    return q, scale
+
+
+def _wq_common(M, K, q, scale, residual, epilogue, out_dtype, out, device):
+    """Argument checks shared by wq_gemv and wq_gemv_rmsnorm -> (out, out code)."""
+    _chk(q, torch.int8, "q", contiguous=False)
+    _chk(scale, torch.float32, "scale")
+    assert q.dim() == 2 and q.stride(1) == 1 and q.shape[1] == K and scale.numel() == q.shape[0], (q.shape, K, scale.shape)
+    N = q.shape[0]
+    No = N // 2 if epilogue == EPI_SWIGLU else N
+    if out is None:
+        out = torch.empty((M, No), dtype=runtime.HALF if out_dtype is None else out_dtype, device=device)
+    else:
+        if out.dtype not in (runtime.HALF, torch.float32):
+            raise TypeError(f"out: expected {runtime.HALF} or torch.float32, got {out.dtype}")
+        _chk(out, out.dtype, "out", contiguous=False)
+        assert tuple(out.shape) == (M, No) and out.stride(1) == 1, (out.shape, (M, No))
+    if residual is not None:
+        _chk(residual, torch.float32, "residual", contiguous=False)
+        assert tuple(residual.shape) == (M, N) and residual.stride(1) == 1
+    return out, (OUT_F32 if out.dtype == torch.float32 else OUT_BF16)
+
+
+def wq_gemv(a, q, scale, residual=None, epilogue=EPI_NONE, out_dtype=None, out=None):
+    """vly_wq_gemv: out[M <= 8, N'] = epi(scale[n] * (a[M, K] @ q[N, K]^T)) + residual over int8 weights ``(q, scale)`` of
+    ``wq_quantize``; EPI_NONE (16-bit or fp32 out) or EPI_SWIGLU (16-bit out)."""
+    from . import lib_wq
+    _chk(a, runtime.HALF, "a", contiguous=False)
+    assert a.dim() == 2 and a.stride(1) == 1, a.shape
+    M, K = a.shape
+    out, od = _wq_common(M, K, q, scale, residual, epilogue, out_dtype, out, a.device)
+    rc = lib_wq.load_wq().vly_wq_gemv(a.data_ptr(), a.stride(0), q.data_ptr(), q.stride(0), scale.data_ptr(), _ptr(residual),
+                                      residual.stride(0) if residual is not None else 0, out.data_ptr(), out.stride(0), M, q.shape[0], K,
+                                      epilogue, od, _wq_dtype(), _stream())
+    lib_wq.check(rc, "vly_wq_gemv")
+    return out
+
+
+def wq_gemv_rmsnorm(h, gamma, eps, q, scale, residual=None, epilogue=EPI_NONE, out_dtype=None, out=None):
+    """vly_wq_gemv_rmsnorm: wq_gemv(rmsnorm(h, gamma, eps), q, scale, ...) in one launch (M <= 2 rows, 2048 <= K <= 6144) —
+    bit-identical to the pair."""
+    from . import lib_wq
+    _chk(h, torch.float32, "h", contiguous=False)
+    _chk(gamma, torch.float32, "gamma")
+    assert h.dim() == 2 and h.stride(1) == 1 and h.shape[1] == gamma.numel(), (h.shape, gamma.shape)
+    M, K = h.shape
+    out, od = _wq_common(M, K, q, scale, residual, epilogue, out_dtype, out, h.device)
+    rc = lib_wq.load_wq().vly_wq_gemv_rmsnorm(h.data_ptr(), h.stride(0), gamma.data_ptr(), eps, q.data_ptr(), q.stride(0),
+                                              scale.data_ptr(), _ptr(residual), residual.stride(0) if residual is not None else 0,
+                                              out.data_ptr(), out.stride(0), M, q.shape[0], K, epilogue, od, _wq_dtype(), _stream())
+    lib_wq.check(rc, "vly_wq_gemv_rmsnorm")
+    return out
+
+
+def wq_gemv_rmsnorm_ok(M: int, K: int) -> bool:
+    """Shapes vly_wq_gemv_rmsnorm takes (the caller keeps rmsnorm + wq_gemv otherwise): gemv_rmsnorm_ok's rule, 16 weights a chunk."""
+    return 1 <= M <= 2 and 2048 <= K <= 6144 and K % 16 == 0

@@ -145,18 +145,21 @@ class ValleyLlamaModel:
     """valley_model.py:21-254."""
     config_class = ValleyConfig
 
-    def __init__(self, config, device="cuda:0"):
+    def __init__(self, config, device="cuda:0", weight_quant=None):
         self.config = config
         self.device = torch.device(device)
         self.training = False
         self.patch_pooling_method = "mean"                   # :27
         c = config
         self.precision = resolve_precision(config)
+        from .llama import resolve_weight_quant
+        wq = resolve_weight_quant(weight_quant, self.precision)      # argument or VALLEY_WEIGHT_QUANT; refused on the fp32 engines
         self.wdtype = torch.float32 if self.precision == "fp32" else runtime.HALF      # dtype of GEMM weights / activations
         engine = PreciseLlama if self.precision == "fp32" else HipLlama
         self.llama = engine(c.hidden_size, c.num_attention_heads, c.intermediate_size, c.num_hidden_layers,
                             c.vocab_size, c.rms_norm_eps, getattr(c, "rope_theta", None) or _rope_theta(c),
-                            getattr(c, "max_position_embeddings", 2048), device=self.device)
+                            getattr(c, "max_position_embeddings", 2048), device=self.device,
+                            **({} if self.precision == "fp32" else {"weight_quant": wq or ""}))      # resolved here: the engine does not read the variable again
         self.vision_tower: Optional[HipCLIPVisionTower] = None
         self.mm_projector: Optional[HipLinear] = None
         self.pooling_layer = None                            # v2: SimpleNamespace(weight fp32 [256*H], bias fp32 [1])
@@ -427,13 +430,13 @@ class ValleyLlamaForCausalLM:
     """valley_model.py:257-439."""
     config_class = ValleyConfig
 
-    def __init__(self, config, device="cuda:0"):
+    def __init__(self, config, device="cuda:0", weight_quant=None):
         from . import lib
         resolve_precision(config)                            # a 16-bit type named by the config picks the library ...
         lib.load()                                           # ... which is loaded here: fail loudly if it is absent
         self.config = config
         self.device = torch.device(device)
-        self.model = ValleyLlamaModel(config, device=device)
+        self.model = ValleyLlamaModel(config, device=device, weight_quant=weight_quant)
 
     # -- module-ish API ------------------------------------------------------------------------------
     def get_model(self):                                     # :269
@@ -528,25 +531,33 @@ class ValleyLlamaForCausalLM:
         return self
 
     @classmethod
-    def from_pretrained(cls, path: str, torch_dtype=None, device="cuda:0", **kw):
-        """Sharded HF checkpoint directory (config.json + *.safetensors / pytorch_model-*.bin)."""
+    def from_pretrained(cls, path: str, torch_dtype=None, device="cuda:0", weight_quant=None, **kw):
+        """Sharded HF checkpoint directory (config.json + *.safetensors / pytorch_model-*.bin).  ``weight_quant="int8"``: the decode
+        steps read int8 projection weights (README "Weight-only INT8 decode")."""
         from .checkpoint import load_valley_checkpoint
         config, sd = load_valley_checkpoint(path, ValleyConfig)
         config.mm_vision_tower_name = getattr(config, "mm_vision_tower", None)
         apply_torch_dtype(config, torch_dtype, "from_pretrained(torch_dtype=%s)" % torch_dtype)
-        return cls.from_state_dict(config, sd, device=device)
+        return cls.from_state_dict(config, sd, device=device, weight_quant=weight_quant)
 
     @classmethod
-    def from_state_dict(cls, config, sd: Dict, device="cuda:0"):
+    def from_state_dict(cls, config, sd: Dict, device="cuda:0", weight_quant=None):
         """Model from an in-memory state dict with the reference's key names (what from_pretrained, the delta tool and
         the LoRA merge all end in)."""
         tower_name = getattr(config, "mm_vision_tower", None)
         if tower_name is not None and not os.path.isdir(str(tower_name)):
             config.mm_vision_tower = None                    # no hub access: the tower must come from the state dict
-        model = cls(config, device=device)
+        model = cls(config, device=device, **({"weight_quant": weight_quant} if weight_quant else {}))
         model.load_state_dict(sd)
         config.mm_vision_tower = tower_name
         return model
+
+    def quantize_decode_weights(self, mode: str = "int8"):
+        """After the fact: the one-token decode steps of this model read int8 copies of the Llama projections from here on
+        (prefill, lm_head, embeddings, norms and the vision tower keep their weights)."""
+        from .llama import resolve_weight_quant
+        self.model.llama.quantize_weights(resolve_weight_quant(mode or "", self.model.precision))
+        return self
 
     # -- forward ---------------------------------------------------------------------------------------
     def forward(self, input_ids=None, attention_mask=None, past_key_values=None, inputs_embeds=None, labels=None,
