@@ -367,13 +367,15 @@ typedef struct {
 } vly_sample_row;
 
 /* Token selection over the last dim of fp32 [M,N] (row stride ld >= N) -> int32 [M].
- *   rows == NULL: argmax, the first maximal index (NaN never selected); serve/model_worker.py:389-391.
+ *   rows == NULL: argmax, the first maximal index (NaN never selected; a row of nothing but NaN gives 0, always a valid
+ *   token id); serve/model_worker.py:389-391.
  *   rows != NULL: rows[r] decides row r.  Greedy rows give the argmax above; the others draw one token, in HF's warper
  *   order: s = x / T; top-k keeps s >= the k-th largest s (ties kept); top-p keeps token t iff the softmax mass of the
  *   kept tokens strictly above s_t is < p; then Gumbel-max, argmax over kept i of s_i - log(-log(u_i)), first index on
  *   ties.  u_i = (2 * (w >> 9) + 1) * 2^-24 with w = word i & 3 of Philox4x32-10 at key (seed_lo, seed_hi), counter
  *   (i >> 2, c, 0, 0), where the draw counter c = (ctr ? ctr[ctr_per_row ? r : 0] : 0) + ctr_add is the index, in the
- *   row's sequence, of the token being drawn.  A row without a finite kept score gives the argmax.  Deterministic: the
+ *   row's sequence, of the token being drawn.  A row without a finite kept score gives the argmax of the logits (0 when
+ *   every logit is NaN or nothing is selectable, on every path).  Deterministic: the
  *   same inputs give the same tokens at every launch (sampling.hip). */
 int vly_argmax(const float *x, int32_t *idx, int M, int N, int ld, const vly_sample_row *rows, const int32_t *ctr,
                int ctr_per_row, int ctr_add, void *stream);

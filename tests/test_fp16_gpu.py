@@ -54,7 +54,8 @@ FP16_KERNEL_DESELECT = {
         "starts its own child on the experimental library (VALLEY_EXPERIMENTAL=1, VLY_LLAMA_ATTN=1)",
 }
 FP16_KERNEL_MODULES = ["tests/test_kernels_gpu.py", "tests/test_r6_gpu.py", "tests/test_gemm_p4_192x384_gpu.py", "tests/test_streamk_gpu.py",
-                       "tests/test_gemm_exact_gpu.py", "tests/test_attention_exact_gpu.py", "tests/test_rows_exact_gpu.py"]
+                       "tests/test_gemm_exact_gpu.py", "tests/test_attention_exact_gpu.py", "tests/test_rows_exact_gpu.py",
+                       "tests/test_sampling_exact_gpu.py"]
 
 
 def test_fp16_library_passes_the_kernel_suites():

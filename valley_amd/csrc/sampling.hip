@@ -19,7 +19,9 @@ namespace {
 
 VLY_DEVICE bool first_max_better(float v, int i, float best, int bi) { return v > best || (v == best && i < bi); }
 
-// block-wide (best value, first index) reduction of 1024 threads; the result is valid in thread 0
+// block-wide (best value, first index) reduction of 1024 threads; the result is valid in thread 0.  When no thread took an
+// element (every value NaN, or nothing selectable) the index is 0, never the 0x7fffffff the threads start from: the token
+// goes straight into the next step's embedding gather.
 VLY_DEVICE int block_first_max(float best, int bi, float* sv, int* si) {
     const int tid = threadIdx.x;
 #pragma unroll
@@ -34,10 +36,11 @@ VLY_DEVICE int block_first_max(float best, int bi, float* sv, int* si) {
         for (int w = 1; w < 16; ++w)
             if (first_max_better(sv[w], si[w], best, bi)) { best = sv[w]; bi = si[w]; }
     }
-    return bi;
+    return bi == 0x7fffffff ? 0 : bi;
 }
 
-// first maximal index of one row (torch.argmax tie rule on CPU; NaN is never selected); valid in thread 0.  16-byte loads
+// first maximal index of one row (torch.argmax tie rule on CPU; NaN is never selected, an all-NaN row gives 0); valid in
+// thread 0.  16-byte loads
 // issued four at a time (a 256-thread scalar loop spent 39 us per 32 k-wide row on dependent load latency: 0.7 % of a
 // 13B decode step).
 VLY_DEVICE int argmax_row(const float* __restrict__ r, int N, float* sv, int* si) {
@@ -58,7 +61,9 @@ VLY_DEVICE int argmax_row(const float* __restrict__ r, int N, float* sv, int* si
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const int i = (c0 + u * 1024 + tid) * 4;
+                const int c = c0 + u * 1024 + tid;
+                if (c >= nv) continue;                      // an absent slot's -inf must not be taken: its index is not the row's
+                const int i = c * 4;
                 take(v[u].x, i); take(v[u].y, i + 1); take(v[u].z, i + 2); take(v[u].w, i + 3);
             }
         }
