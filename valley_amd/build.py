@@ -27,7 +27,12 @@ LOGITS_SOURCES = ["logits.hip"]
 # 16-bit storage types (every compute entry takes the dtype code), so the main libraries' exports stay exactly valley_hip.h's
 LIB_WQ = os.path.join(LIBDIR, "libvalley_hip_wq.so")
 WQ_SOURCES = ["wq.hip"]
-# the row top-K and merge that both companions compile (beam candidates over log-softmax and over processed scores)
+# token log-probabilities and the forward-only loss (include/valley_hip_score.h): fp32 logits and int32 ids only, like the logits
+# processors, whose log-sum-exp routine (beam_rows.inc) it compiles; loaded on first use
+LIB_SCORE = os.path.join(LIBDIR, "libvalley_hip_score.so")
+SCORE_SOURCES = ["score.hip"]
+# the row top-K and merge that the beam and logits companions compile (beam candidates over log-softmax and over processed
+# scores), and the log-sum-exp routine the score companion shares with them
 COMPANION_SHARED = ["beam_rows.inc"]
 SOURCES = ["capi.hip", "gemm_bf16.hip", "gemm_p32.hip", "gemm_p16.hip", "gemm_streamk.hip", "norm_elementwise.hip", "attention.hip", "temporal_delta.hip", "preprocess.hip", "gemv_bf16.hip", "precise_f32.hip", "gemm_skinny.hip", "decode_step.hip", "sampling.hip"]
 
@@ -44,8 +49,9 @@ def hipcc() -> str:
 
 def needs_build() -> bool:
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h)
-                                                                 for h in ("valley_hip.h", "valley_hip_beam.h", "valley_hip_logits.h", "valley_hip_wq.h")]
-    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, LIB_BEAM, LIB_LOGITS, LIB_WQ):
+                                                                 for h in ("valley_hip.h", "valley_hip_beam.h", "valley_hip_logits.h", "valley_hip_wq.h",
+                                                                           "valley_hip_score.h")]
+    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, LIB_BEAM, LIB_LOGITS, LIB_WQ, LIB_SCORE):
         if not os.path.exists(lib):
             return True
         t = os.path.getmtime(lib)
@@ -63,6 +69,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(os.path.join(LIBDIR, "beam"), exist_ok=True)
     os.makedirs(os.path.join(LIBDIR, "logits"), exist_ok=True)
     os.makedirs(os.path.join(LIBDIR, "wq"), exist_ok=True)
+    os.makedirs(os.path.join(LIBDIR, "score"), exist_ok=True)
     if not force and not needs_build():
         return LIB
     variants = [(LIB, LIBDIR, [], SOURCES), (LIB_F16, os.path.join(LIBDIR, "f16"), ["-DVLY_FP16=1"], SOURCES),
@@ -91,7 +98,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
             if s in AUDITED:
                 audits.append((s, odir, " ".join(flags) or "(default flags)"))
     companions = [(LIB_BEAM, "beam", BEAM_SOURCES, "valley_hip_beam.h"), (LIB_LOGITS, "logits", LOGITS_SOURCES, "valley_hip_logits.h"),
-                  (LIB_WQ, "wq", WQ_SOURCES, "valley_hip_wq.h")]
+                  (LIB_WQ, "wq", WQ_SOURCES, "valley_hip_wq.h"), (LIB_SCORE, "score", SCORE_SOURCES, "valley_hip_score.h")]
     for _lib, sub, units, header in companions:
         cdir = os.path.join(LIBDIR, sub)
         for s in units:

@@ -39,7 +39,7 @@ SPLIT_ROWS = os.environ.get("VALLEY_DECODE_SPLIT_ROWS", "1") != "0"       # roun
 class DecodeSession:
     def __init__(self, llama: HipLlama, cache: HipKVCache, use_graph: bool = True, per_row_positions: bool = False,
                  sampling: bool = False, beams: Optional[tuple] = None, processors: bool = False,
-                 processor_eos: Optional[Sequence[int]] = None):
+                 processor_eos: Optional[Sequence[int]] = None, logprobs: Optional[int] = None):
         """``per_row_positions``: every batch row is an independent sequence at its own position (``pos`` is int32 [B]
         and advances by one per step for every row) — the captured step of valley_amd.serving.ContinuousBatcher.
         ``sampling``: the step draws each row's next token with that row's parameters in ``self.sample`` (int32 [B, 6],
@@ -58,12 +58,26 @@ class DecodeSession:
         ``begin(prompt_ids=...)`` or by the caller per slot, then every token fed to a step, appended on the device).  The
         EOS ids of the minimum length are ``processor_eos`` (default: a beam session's EOS ids).  With beams the step runs
         the history gather (rows follow their parents over [S, pos)), the processors on log_softmax(logits) and the
-        candidates over those scores (ops.logits_beam_candidates) instead of ops.beam_candidates."""
+        candidates over those scores (ops.logits_beam_candidates) instead of ops.beam_candidates.
+        ``logprobs = n`` (0 <= n <= 20): the step records log_softmax(raw logits)[chosen token] of every row in
+        ``self.lp_table`` (fp32 [B, ctx_max + 1], column = the token's index in the row's sequence, ``pos + 1``: the step
+        at the cache's last position chooses the token of index ctx_max) and, for n > 0, the n most probable ids and their
+        log-probabilities in ``self.lp_top_tables`` (int32 / fp32 [B, ctx_max + 1, n]):
+        ops.token_logprobs right behind the lm_head, ops.score_record behind the argmax / draw.  The processors and the
+        sampler rewrite the logits in place before the token is known, so with either the raw row is copied aside
+        (``self.lp_raw``).  A token the caller picks itself (host sampling) is recorded by ``record_token()``."""
         self.ll, self.cache = llama, cache
         B, d = cache.batch, llama.device
         if B > 8:
             raise ValueError("decode sessions stream weights with the GEMV kernel: batch <= 8")
         self.B = B
+        if logprobs is not None:
+            if beams is not None:
+                raise ValueError("beam sessions take no logprobs: beam search reports sequences_scores")
+            if PERSISTENT:
+                raise ValueError("the persistent decode step (VALLEY_DECODE_PERSISTENT=1) takes no logprobs: unset it")
+            if not 0 <= int(logprobs) <= ops.SCORE_MAX_TOP:
+                raise ValueError(f"logprobs must be in [0, {ops.SCORE_MAX_TOP}] (the number of alternatives per token), got {logprobs!r}")
         self.wq = bool(getattr(llama, "weight_quant", None))     # the four projections of every layer stream int8 weights
         if self.wq and (PERSISTENT or MERGE_IN == "oproj"):
             raise ValueError("an int8-quantized engine decodes with the per-layer launches only: unset VALLEY_DECODE_PERSISTENT and "
@@ -115,6 +129,18 @@ class DecodeSession:
                 processor_eos = beams[3]
             if processor_eos:
                 self.proc_eos = torch.tensor([int(e) for e in processor_eos], dtype=torch.int32, device=d)
+        self.lp_n = None
+        if logprobs is not None:
+            self.lp_n = n = int(logprobs)
+            self.lp_lse = torch.zeros((B,), dtype=torch.float32, device=d)
+            self.lp_table = torch.zeros((B, cache.ctx_max + 1), dtype=torch.float32, device=d)
+            self.lp_top = self.lp_top_tables = None
+            if n:
+                self.lp_top = (torch.full((B, n), -1, dtype=torch.int32, device=d), torch.zeros((B, n), dtype=torch.float32, device=d))
+                self.lp_top_tables = (torch.full((B, cache.ctx_max + 1, n), -1, dtype=torch.int32, device=d),
+                                      torch.zeros((B, cache.ctx_max + 1, n), dtype=torch.float32, device=d))
+            # in place before the token is picked: the processors' rescaling and bans, the sampler's temperature and filters
+            self.lp_raw = torch.empty((B, llama.V), dtype=torch.float32, device=d) if (processors or sampling) else None
         self.use_graph = use_graph
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._gen = cache.generation
@@ -200,13 +226,28 @@ class DecodeSession:
             if tail:
                 self.beam_tail()
             return
+        if self.lp_n is not None:                    # lse (and the top-n) of the raw logits, before anything rewrites them
+            ops.token_logprobs(self.logits[:, :ll.V], top=self.lp_n, out_lse=self.lp_lse, copy=self.lp_raw, out_top=self.lp_top)
         if self.proc is not None:                    # the token fed to this step joins the history at index pos
             ops.logits_process(self.logits[:, :ll.V], self.proc, self.hist, self.pos, 1, tok=self.tok, eos=self.proc_eos)
         if self.sample is None:
             ops.argmax(self.logits[:, :ll.V], out=self.tok)
         else:
             ops.argmax(self.logits[:, :ll.V], sampling=self.sample, ctr=self.pos, ctr_add=1, out=self.tok)
+        if self.lp_n is not None:                    # the token just chosen has index pos + 1 in its row's sequence
+            self._record(1)
         ops.incr_i32(self.pos, 1)
+
+    def _record(self, len_add: int):
+        ops.score_record(self.lp_raw if self.lp_raw is not None else self.logits[:, :self.ll.V], self.lp_lse, self.tok, self.lp_table,
+                         self.pos, len_add, top=self.lp_top, top_tables=self.lp_top_tables)
+
+    def record_token(self):
+        """After ``step()``, for a caller that picked the token itself and wrote it into ``self.tok`` (host sampling): the
+        step's column of ``self.lp_table`` is rewritten for that token (``pos`` has advanced: the column is ``pos``)."""
+        if self.lp_n is None:
+            raise ValueError("record_token() needs DecodeSession(..., logprobs=n)")
+        self._record(0)
 
     def _o_proj(self, L):
         if self.wq:
@@ -235,6 +276,16 @@ class DecodeSession:
             h[:, :self.hist.shape[1]].copy_(self.hist)
             self.hist = h
             self._gen = None                                 # a graph holds the old history's pointer: capture again
+        if self.lp_n is not None and self.lp_table.shape[1] < self.cache.ctx_max + 1:    # the log-probability tables likewise
+            old = [self.lp_table] + list(self.lp_top_tables or ())
+            new = [torch.full((self.B, self.cache.ctx_max + 1) + tuple(t.shape[2:]), -1 if t.dtype == torch.int32 else 0, dtype=t.dtype,
+                              device=t.device) for t in old]
+            for t, u in zip(old, new):
+                u[:, :t.shape[1]].copy_(t)
+            self.lp_table = new[0]
+            if self.lp_top_tables is not None:
+                self.lp_top_tables = (new[1], new[2])
+            self._gen = None
 
     def begin(self, first_token: Optional[torch.Tensor] = None, prompt_ids: Optional[torch.Tensor] = None):
         """Call after the prefill filled ``cache``: sets the device position and the first input token (per-row sessions
@@ -264,6 +315,9 @@ class DecodeSession:
         pos0, tok0 = self.pos.clone(), self.tok.clone()
         beam0 = None
         hist0 = None if self.hist is None else self.hist.clone()   # the warm-up step appends / gathers: restored
+        lp0 = None
+        if self.lp_n is not None:                            # the warm-up step records a column: restored
+            lp0 = [(t, t.clone()) for t in [self.lp_table] + list(self.lp_top_tables or ())]
         if self.beams is not None:                           # the warm-up step also moves the beams: restored with the rest
             beam0 = [self.parent.clone(), self.running.clone()] + [t.clone() for t in self.cand]
             S, hi = self.beams[2], self.cache.seq_len + 1
@@ -276,6 +330,8 @@ class DecodeSession:
         self.tok.copy_(tok0)
         if hist0 is not None:
             self.hist.copy_(hist0)
+        for t, t0 in lp0 or ():
+            t.copy_(t0)
         if beam0 is not None:
             for t, t0 in zip([self.parent, self.running] + list(self.cand), beam0):
                 t.copy_(t0)

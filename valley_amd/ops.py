@@ -1518,6 +1518,136 @@ def logits_beam_candidates(scores: torch.Tensor, running: torch.Tensor, B: int, 
     return out
 
 
+# ---- token log-probabilities and the forward-only loss (libvalley_hip_score.so, include/valley_hip_score.h) ----------------
+SCORE_MAX_TOP = 20       # VLY_SCORE_MAX_TOP
+SCORE_MAX_V = 1 << 18
+
+
+def token_logprobs(logits: torch.Tensor, targets: Optional[torch.Tensor] = None, top: int = 0,
+                   out_lse: Optional[torch.Tensor] = None, copy: Optional[torch.Tensor] = None,
+                   out_target: Optional[torch.Tensor] = None, out_top=None):
+    """logits fp32 [R, V] (row stride may exceed V; read only) -> ``(target_lp | None, lse, top_id | None, top_lp | None)``.
+    ``lse`` fp32 [R] is the row's log-sum-exp over its non-NaN values (0 when its maximum is not finite), with the bits of
+    ``logits_process(log_softmax=True)``.  ``targets`` int32 [R]: target_lp[r] = x[r, t] - lse[r], 0 for an id outside
+    [0, V) (-100 included).  ``top`` in [0, 20]: the ``top`` largest non-NaN values of every row, best first, ties to the
+    lower index, as ids int32 [R, top] and x - lse fp32 [R, top]; a row with fewer ends in -1 / -inf.  ``copy`` fp32
+    [R, >= V]: receives columns [0, V) unchanged.  ``out_lse`` / ``out_target`` / ``out_top = (ids, lps)``: caller-owned
+    outputs (a captured step's buffers)."""
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        raise ValueError(f"token_logprobs: logits [R, V] with unit column stride and a row stride >= V expected, got "
+                         f"{tuple(logits.shape)} with strides {tuple(logits.stride())}")
+    R, V = logits.shape
+    top = int(top)
+    if not 0 <= top <= SCORE_MAX_TOP:
+        raise ValueError(f"token_logprobs: top must be in [0, {SCORE_MAX_TOP}], got {top}")
+    if not 0 < V <= SCORE_MAX_V or R <= 0:
+        raise ValueError(f"token_logprobs: 0 < V <= {SCORE_MAX_V} and R > 0 expected, got R={R} V={V}")
+    if targets is not None and targets.numel() != R:
+        raise ValueError(f"token_logprobs: targets must hold {R} values, got {targets.numel()}")
+    if copy is not None and (copy.dim() != 2 or copy.shape[0] != R or copy.shape[1] < V or copy.stride(1) != 1):
+        raise ValueError(f"token_logprobs: copy [{R}, >= {V}] with unit column stride expected, got {tuple(copy.shape)}")
+    if out_target is not None and targets is None:
+        raise ValueError("token_logprobs: out_target needs targets")
+    if out_top is not None and (top == 0 or len(out_top) != 2 or any(tuple(t.shape) != (R, top) for t in out_top)):
+        raise ValueError(f"token_logprobs: out_top must be (ids, lps) of shape [{R}, {top}] with top > 0")
+    from . import lib_score
+    _chk(logits, torch.float32, "logits", contiguous=False)
+    d = logits.device
+    tlp = None
+    if targets is not None:
+        _chk(targets, torch.int32, "targets")
+        tlp = torch.empty((R,), dtype=torch.float32, device=d) if out_target is None else out_target
+        _chk(tlp, torch.float32, "out_target")
+        if tlp.numel() != R:
+            raise ValueError(f"token_logprobs: out_target must hold {R} values")
+    lse = torch.empty((R,), dtype=torch.float32, device=d) if out_lse is None else out_lse
+    _chk(lse, torch.float32, "out_lse")
+    if lse.numel() != R:
+        raise ValueError(f"token_logprobs: out_lse must hold {R} values")
+    tid = tl = None
+    if top:
+        tid, tl = out_top if out_top is not None else (torch.empty((R, top), dtype=torch.int32, device=d),
+                                                       torch.empty((R, top), dtype=torch.float32, device=d))
+        _chk(tid, torch.int32, "top ids")
+        _chk(tl, torch.float32, "top log-probabilities")
+    if copy is not None:
+        _chk(copy, torch.float32, "copy", contiguous=False)
+    rc = lib_score.load_score().vly_score_rows(logits.data_ptr(), logits.stride(0), V, R, _ptr(targets), _ptr(tlp), lse.data_ptr(),
+                                               top, _ptr(tid), _ptr(tl), _ptr(copy), copy.stride(0) if copy is not None else 0,
+                                               _stream())
+    lib_score.check(rc, "vly_score_rows")
+    return tlp, lse, tid, tl
+
+
+def score_record(raw: torch.Tensor, lse: torch.Tensor, tok: torch.Tensor, lp_table: torch.Tensor,
+                 length: Optional[torch.Tensor] = None, len_add: int = 0, top=None, top_tables=None) -> None:
+    """The decode step's tail: lp_table[r, c] = raw[r, tok[r]] - lse[r] (0 for a token outside [0, V)) over raw fp32 [R, V]
+    (row stride may exceed V), lse fp32 [R], tok int32 [R] and the fp32 [R, L] table; ``top = (ids, lps)`` [R, n] go to
+    ``top_tables = (ids, lps)`` [R, L, n] at the same column.  c = ``length[r]`` (int32 [R]) or ``length[0]`` (int32 [1]),
+    plus ``len_add``, read on the device; a row whose c is outside [0, L) writes nothing."""
+    if raw.dim() != 2 or raw.stride(1) != 1 or raw.stride(0) < raw.shape[1]:
+        raise ValueError(f"score_record: raw [R, V] with unit column stride and a row stride >= V expected, got "
+                         f"{tuple(raw.shape)} with strides {tuple(raw.stride())}")
+    R, V = raw.shape
+    if lse.numel() != R or tok.numel() != R or lp_table.dim() != 2 or lp_table.shape[0] != R:
+        raise ValueError(f"score_record: lse [{R}], tok [{R}] and lp_table [{R}, L] expected, got {tuple(lse.shape)} / "
+                         f"{tuple(tok.shape)} / {tuple(lp_table.shape)}")
+    L = lp_table.shape[1]
+    if (top is None) != (top_tables is None):
+        raise ValueError("score_record: top and top_tables go together")
+    n = 0
+    if top is not None:
+        n = top[0].shape[-1]
+        if not 0 < n <= SCORE_MAX_TOP or any(tuple(t.shape) != (R, n) for t in top) or \
+                any(tuple(t.shape) != (R, L, n) for t in top_tables):
+            raise ValueError(f"score_record: top (ids, lps) [{R}, n <= {SCORE_MAX_TOP}] and top_tables [{R}, {L}, n] expected")
+    if length is not None and length.numel() not in (1, R):
+        raise ValueError(f"score_record: length must hold 1 or {R} values, got {length.numel()}")
+    from . import lib_score
+    _chk(raw, torch.float32, "raw", contiguous=False)
+    _chk(lse, torch.float32, "lse")
+    _chk(tok, torch.int32, "tok")
+    _chk(lp_table, torch.float32, "lp_table")
+    lptr, per_row = None, 0
+    if length is not None:
+        _chk(length, torch.int32, "length")
+        lptr, per_row = length.data_ptr(), int(length.numel() == R and R > 1)
+    ptrs = [None] * 4
+    if top is not None:
+        for t, dt, name in zip(list(top) + list(top_tables), (torch.int32, torch.float32) * 2,
+                               ("top ids", "top log-probabilities", "top id table", "top log-probability table")):
+            _chk(t, dt, name)
+        ptrs = [t.data_ptr() for t in list(top) + list(top_tables)]
+    rc = lib_score.load_score().vly_score_record(raw.data_ptr(), raw.stride(0), V, R, lse.data_ptr(), tok.data_ptr(), lptr, per_row,
+                                                 int(len_add), lp_table.data_ptr(), L, n, *ptrs, _stream())
+    lib_score.check(rc, "vly_score_record")
+
+
+def cross_entropy(logits: torch.Tensor, labels: torch.Tensor):
+    """torch.nn.functional.cross_entropy(logits, labels, ignore_index=-100) without gradients, over logits fp32 [M, V] (row
+    stride may exceed V) and labels int32 [M] -> ``(loss, count)``: loss a 0-d fp32 tensor, the mean of -log_softmax at the
+    labels in [0, V) (accumulated in float64 in a fixed order, NaN when none counts), count a 0-d int32 tensor."""
+    if logits.dim() != 2 or labels.numel() != logits.shape[0]:
+        raise ValueError(f"cross_entropy: logits [M, V] and labels [M] expected, got {tuple(logits.shape)} / {tuple(labels.shape)}")
+    tlp, _, _, _ = token_logprobs(logits, labels.reshape(-1))
+    return nll_mean(tlp, labels.reshape(-1), logits.shape[1])
+
+
+def nll_mean(target_lp: torch.Tensor, targets: torch.Tensor, V: int):
+    """``(loss, count)`` of ``cross_entropy`` from the per-row log-probabilities ``token_logprobs`` returned for ``targets``."""
+    if target_lp.numel() != targets.numel() or target_lp.numel() == 0:
+        raise ValueError(f"nll_mean: as many log-probabilities as targets (> 0) expected, got {target_lp.numel()} / {targets.numel()}")
+    from . import lib_score
+    _chk(target_lp, torch.float32, "target_lp")
+    _chk(targets, torch.int32, "targets")
+    loss = torch.empty((), dtype=torch.float32, device=target_lp.device)
+    count = torch.empty((), dtype=torch.int32, device=target_lp.device)
+    rc = lib_score.load_score().vly_score_loss(target_lp.data_ptr(), targets.data_ptr(), target_lp.numel(), int(V), loss.data_ptr(),
+                                               count.data_ptr(), _stream())
+    lib_score.check(rc, "vly_score_loss")
+    return loss, count
+
+
 # ---- weight-only INT8 decode (libvalley_hip_wq.so, include/valley_hip_wq.h) ------------------------------------------------
 def _wq_dtype() -> int:
     return 1 if runtime.HALF == torch.float16 else 0          # the codes of vly_storage_dtype

@@ -110,13 +110,18 @@ class ContinuousBatcher:
     and ignored: the GEMV cost does not depend on the row count), clamped inside their cache rows."""
 
     def __init__(self, model, slots: int = 4, ctx_max: int = 1024, use_graph: bool = True, sampling: bool = False,
-                 processors: bool = False, eos_token_id=None):
+                 processors: bool = False, eos_token_id=None, logprobs: Optional[int] = None):
         """``sampling``: the captured step draws every slot's token with the parameters ``add`` gave its request
         (temperature, top-k, top-p, seed; DecodeSession ``sampling``) — a seeded request's tokens then depend on its seed
         alone, not on its slot or its neighbours.  Greedy requests take the argmax in either kind of batcher.
         ``processors``: the captured step runs HF's repetition penalty, no-repeat n-grams and minimum new tokens with the
         parameters ``add`` gave each request (DecodeSession ``processors``), over the slot's history (its prompt, then its
-        tokens); ``eos_token_id`` (an int or a list) is what ``min_new_tokens`` keeps out."""
+        tokens); ``eos_token_id`` (an int or a list) is what ``min_new_tokens`` keeps out.
+        ``logprobs = n`` (0 <= n <= 20): every token's log_softmax(raw logits)[token] and the n most probable alternatives
+        (DecodeSession ``logprobs``).  ``add`` leaves the first token's in ``self.first_logprobs[slot]``, ``step`` the step's
+        in ``self.last_logprobs`` — ``{slot: (lp, top ids, top lps)}`` — and the slot's row of ``self.sess.lp_table``
+        (column = the token's index in the request's sequence) keeps them all.  A request's values do not depend on its slot
+        or its neighbours."""
         if not 1 <= slots <= 8:
             raise ValueError("1 <= slots <= 8 (the decode step streams weights with the GEMV kernels)")
         self.model, self.ll = model, model.get_model().llama
@@ -131,7 +136,9 @@ class ContinuousBatcher:
         self.processors = processors
         eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id])
         self.sess = DecodeSession(self.ll, self.cache, use_graph=use_graph, per_row_positions=True, sampling=sampling,
-                                  processors=processors, processor_eos=eos)
+                                  processors=processors, processor_eos=eos, **({} if logprobs is None else {"logprobs": logprobs}))
+        self.logprobs = None if logprobs is None else int(logprobs)
+        self.first_logprobs, self.last_logprobs = {}, {}
         self.live = [False] * slots
         self.length = [0] * slots                                # tokens in each slot's cache (host mirror of sess.pos)
         self._captured = False
@@ -175,6 +182,12 @@ class ContinuousBatcher:
         row = type(self.cache).rows_of(self.cache, slot, slot + 1)
         out = self.model(input_ids=ids, images=images, attention_mask=attention_mask, past_key_values=row, use_cache=True)
         last = out.logits[0, -1:]
+        scored = None
+        if self.logprobs is not None:                            # the raw logits: before the processors and the draw rewrite them
+            last = last.float().contiguous()
+            raw = torch.empty_like(last) if (proc is not None or params is not None) else last
+            _, lse, tid, tl = ops.token_logprobs(last, top=self.logprobs, copy=None if raw is last else raw)
+            scored = (raw, lse, tid, tl)
         if proc is not None:                                     # the slot's history: the prompt; the first token is processed
             self.sess.proc[slot:slot + 1].copy_(proc)
             self.sess.hist[slot, :S] = ids[0].to(torch.int32)
@@ -190,6 +203,12 @@ class ContinuousBatcher:
             self.sess.sample[slot:slot + 1].copy_(params)
         self.sess.pos[slot:slot + 1].fill_(S)
         self.sess.tok[slot:slot + 1].fill_(tok)
+        if scored is not None:                                   # the first token sits at index S of the request's sequence
+            raw, lse, tid, tl = scored
+            tabs = None if not self.logprobs else tuple(t[slot:slot + 1] for t in self.sess.lp_top_tables)
+            ops.score_record(raw, lse, self.sess.tok[slot:slot + 1], self.sess.lp_table[slot:slot + 1], None, S,
+                             top=(tid, tl) if self.logprobs else None, top_tables=tabs)
+            self.first_logprobs[slot] = self._read_logprobs(self.sess.lp_table[slot:slot + 1, S:S + 1], (tid, tl))[0]
         self.live[slot], self.length[slot] = True, S
         self.last_prefill_logits = last[0]
         return slot
@@ -209,12 +228,29 @@ class ContinuousBatcher:
             return {}
         self.sess.step()
         toks = self.sess.tok.tolist()                            # one D2H read per step for all requests
+        rows = None
+        if self.logprobs is not None:                            # ... and one more for their log-probabilities: the step's column
+            # pos has advanced to the chosen token's index, at most ctx_max for a live slot: the tables' last column.  (An idle
+            # slot's counter runs on; the bound only keeps its ignored read inside the table.)
+            col = self.sess.pos.long().clamp(0, self.ctx_max)[:, None]
+            rows = self._read_logprobs(self.sess.lp_table.gather(1, col), self.sess.lp_top)
+            self.last_logprobs = {}
         out = {}
         for i in range(self.slots):
             if self.live[i]:
                 self.length[i] += 1
                 out[i] = toks[i]
+                if rows is not None:
+                    self.last_logprobs[i] = rows[i]
         return out
+
+    def _read_logprobs(self, lp, top):
+        """lp fp32 [R, 1] and the step's top-n rows -> [(lp, ids, lps)] per row, through ONE device-to-host copy"""
+        n = self.logprobs
+        packed = lp if not n else torch.cat([lp, top[1], top[0].view(torch.float32)], dim=1)
+        host = packed.cpu()
+        return [(float(host[r, 0]), host[r, 1 + n:].contiguous().view(torch.int32).tolist() if n else [],
+                 host[r, 1:1 + n].tolist() if n else []) for r in range(host.shape[0])]
 
     def release(self, slot: int) -> None:
         if self._captured and self.live[slot]:

@@ -562,9 +562,17 @@ class ValleyLlamaForCausalLM:
     # -- forward ---------------------------------------------------------------------------------------
     def forward(self, input_ids=None, attention_mask=None, past_key_values=None, inputs_embeds=None, labels=None,
                 use_cache=None, output_attentions=None, output_hidden_states=None, images=None, return_dict=None, **kw):
-        """valley_model.py:272-330.  Returns CausalLMOutputWithPast(logits fp32 [B,S,V], past_key_values)."""
+        """valley_model.py:272-330.  Returns CausalLMOutputWithPast(logits fp32 [B,S,V], past_key_values).
+        ``labels`` [B, S] (aligned with ``input_ids``: the visual splice is in place): ``.loss`` is the reference's shifted
+        cross-entropy (:307-318) — the logits at positions [:-1] against labels[:, 1:], ignore index -100, the mean over the
+        counted tokens, NaN when none counts (a single position included: nothing is left after the shift) — computed
+        forward-only on the device (ops.token_logprobs / ops.nll_mean, the two halves of ops.cross_entropy; no gradients).
+        The labels' shape is checked before anything is launched."""
         if labels is not None:
-            raise NotImplementedError("training loss (valley_model.py:307-318) is outside the inference hot path")
+            ref = input_ids if input_ids is not None else inputs_embeds
+            if ref is not None and tuple(labels.shape) != tuple(ref.shape[:2]):
+                raise ValueError(f"forward: labels must be [B, S] = {list(ref.shape[:2])} (aligned with the input positions), got "
+                                 f"{list(labels.shape)}")
         # one launch sequence per stream at a time (the reference's worker calls the model from a thread pool,
         # serve/model_worker.py:467-474); requests on different HIP streams run concurrently
         with runtime.stream_lock():
@@ -574,13 +582,48 @@ class ValleyLlamaForCausalLM:
             hidden = out.last_hidden_state                                    # bf16 [B,S,H] (a workspace view)
             B, S, H = hidden.shape
             logits = self.model.llama.logits(hidden.view(B * S, H)).view(B, S, -1)  # lm_head on ALL positions (:304-305)
+            loss = None
+            if labels is not None:
+                if tuple(labels.shape) != (B, S):
+                    raise ValueError(f"forward: labels must be [B, S] = [{B}, {S}] (aligned with the input positions), got "
+                                     f"{tuple(labels.shape)}")
+                if S < 2:                                    # the shift leaves no token: the reference's mean over none
+                    loss = torch.full((), float("nan"), dtype=torch.float32, device=logits.device)
+                else:
+                    tlp, tgt = self._shifted_logprobs(logits, labels)
+                    loss, _ = ops.nll_mean(tlp.view(-1), tgt.view(-1), logits.shape[-1])
         if return_dict is False:
-            return (logits, out.past_key_values)
-        return CausalLMOutputWithPast(loss=None, logits=logits, past_key_values=out.past_key_values,
+            return (logits, out.past_key_values) if loss is None else (loss, logits, out.past_key_values)
+        return CausalLMOutputWithPast(loss=loss, logits=logits, past_key_values=out.past_key_values,
                                       hidden_states=getattr(out, "hidden_states", None),
                                       attentions=getattr(out, "attentions", None))
 
     __call__ = forward
+
+    def _shifted_logprobs(self, logits, labels):
+        """-> (log_softmax(logits[:, :-1])[labels[:, 1:]] fp32 [B, S - 1], 0 where the label is ignored; those labels int32)"""
+        B, S, V = logits.shape
+        tgt = labels.to(self.device)[:, 1:].to(torch.int32).contiguous()
+        tlp = torch.empty((B, S - 1), dtype=torch.float32, device=logits.device)
+        for b in range(B):                                   # one launch per sequence: no copy of the [B, S, V] logits
+            ops.token_logprobs(logits[b, :-1], tgt[b], out_target=tlp[b])
+        return tlp, tgt
+
+    @torch.no_grad()
+    def score(self, input_ids, labels=None, images=None, attention_mask=None):
+        """Log-probabilities of given tokens under the model (perplexity, multiple-choice scoring): one forward over
+        ``input_ids`` [B, S], then ``token_logprobs`` fp32 [B, S - 1] = log_softmax(logits[:, i])[labels[:, i + 1]], 0 where
+        the label is ignored (-100, or any id outside the vocabulary); ``sum`` fp32 [B] (added in float64) and ``count``
+        int64 [B] per row.  ``labels=None`` scores every position of ``input_ids`` (left padding included: mask it with
+        -100 labels)."""
+        input_ids = input_ids.to(self.device)
+        labels = input_ids if labels is None else labels
+        if tuple(labels.shape) != tuple(input_ids.shape) or input_ids.shape[1] < 2:
+            raise ValueError(f"score: labels must have input_ids' shape [B, S >= 2], got {tuple(labels.shape)} / {tuple(input_ids.shape)}")
+        out = self.forward(input_ids=input_ids, images=images, attention_mask=attention_mask)
+        tlp, tgt = self._shifted_logprobs(out.logits, labels)
+        counted = (tgt >= 0) & (tgt < out.logits.shape[-1])
+        return SimpleNamespace(token_logprobs=tlp, sum=tlp.double().sum(dim=1).float(), count=counted.sum(dim=1))
 
     def prepare_inputs_for_generation(self, input_ids, past_key_values=None, attention_mask=None, inputs_embeds=None, **kwargs):
         """valley_model.py:332-352 (an EMPTY HipKVCache is falsy, so step 0 keeps the whole prompt — the
@@ -600,7 +643,8 @@ class ValleyLlamaForCausalLM:
                  temperature: float = 1.0, stopping_criteria=None, eos_token_id=None, use_graph=True, top_k=None, top_p=None,
                  seed=None, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False,
                  num_return_sequences: int = 1, return_dict_in_generate: bool = False, repetition_penalty=None,
-                 no_repeat_ngram_size=None, min_length=None, min_new_tokens=None, **kw):
+                 no_repeat_ngram_size=None, min_length=None, min_new_tokens=None, output_logprobs: bool = False,
+                 top_logprobs: int = 0, **kw):
         """Prefill + per-token KV decode (the loop of serve/model_worker.py:371-394; the reference's CLI
         path reaches the same through HF ``generate``, valley_model.py:432).  Greedy when not sampling or
         temperature < 1e-4, else temperature softmax + multinomial.  Decode steps run through a
@@ -621,8 +665,25 @@ class ValleyLlamaForCausalLM:
         tokens; with beams they see log_softmax(logits).  They run on the device (ops.logits_process), inside the captured
         step too; the minimum lengths need ``eos_token_id``.  Greedy and sampling take them for any row count; beam search
         takes them within its own limit (the KV reorder moves at most 128 rows of 16-bit or 64 rows of fp32 cache).  Left at
-        their defaults, nothing changes."""
+        their defaults, nothing changes.
+
+        ``output_logprobs`` (with ``return_dict_in_generate``): the result gains ``token_logprobs`` fp32 [B, new tokens] =
+        log_softmax(raw model logits)[token] — before the processors, the temperature and top-k / top-p; HF's
+        ``compute_transition_scores(sequences, out.logits, normalize_logits=True)`` — and, with ``top_logprobs = n`` in
+        [1, 20], ``top_tokens`` int32 / ``top_logprobs`` fp32 [B, new tokens, n], the n most probable ids, best first.
+        Entries behind a row's end (its pad tokens) are 0, with ids -1.  Computed on the device (ops.token_logprobs /
+        ops.score_record), inside the captured step too, and read once after the loop.  Not with beams."""
         proc = (repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens)
+        top_logprobs = 0 if top_logprobs is None else int(top_logprobs)
+        if (output_logprobs or top_logprobs) and not return_dict_in_generate:
+            raise ValueError("output_logprobs / top_logprobs need return_dict_in_generate=True (the log-probabilities are "
+                             "returned on that object)")
+        if top_logprobs and not output_logprobs:
+            raise ValueError("top_logprobs needs output_logprobs=True")
+        if not 0 <= top_logprobs <= ops.SCORE_MAX_TOP:
+            raise ValueError(f"top_logprobs must be in [0, {ops.SCORE_MAX_TOP}], got {top_logprobs}")
+        if output_logprobs and num_beams is not None and int(num_beams) > 1:
+            raise ValueError("output_logprobs is not supported with num_beams > 1: beam search reports sequences_scores")
         if num_beams is None or int(num_beams) < 1:
             raise ValueError(f"num_beams must be >= 1, got {num_beams!r}")
         if int(num_beams) > 1:
@@ -636,9 +697,13 @@ class ValleyLlamaForCausalLM:
             return SimpleNamespace(sequences=seq, sequences_scores=scores) if return_dict_in_generate else seq
         if num_return_sequences != 1:
             raise ValueError("num_return_sequences > 1 needs num_beams > 1 (sampling several sequences per prompt is not supported)")
+        lp_out = {} if output_logprobs else None
         seq = self._generate(input_ids, images, attention_mask, max_new_tokens, do_sample, temperature, stopping_criteria,
-                             eos_token_id, use_graph, top_k, top_p, seed, proc=proc, **kw)
-        return SimpleNamespace(sequences=seq, sequences_scores=None) if return_dict_in_generate else seq
+                             eos_token_id, use_graph, top_k, top_p, seed, proc=proc, logprobs=top_logprobs if output_logprobs else None,
+                             lp_out=lp_out, **kw)
+        if not return_dict_in_generate:
+            return seq
+        return SimpleNamespace(sequences=seq, sequences_scores=None, **(lp_out or {}))
 
     @staticmethod
     def _processor_table(proc, S: int, eos_ids, device) -> Optional[torch.Tensor]:
@@ -655,7 +720,7 @@ class ValleyLlamaForCausalLM:
         return table.to(device)
 
     def _generate(self, input_ids, images, attention_mask, max_new_tokens, do_sample, temperature, stopping_criteria, eos_token_id,
-                  use_graph, top_k, top_p, seed, proc=None, **kw):
+                  use_graph, top_k, top_p, seed, proc=None, logprobs=None, lp_out=None, **kw):
         input_ids = input_ids.to(self.device)
         B, S = input_ids.shape
         ctx = min(getattr(self.config, "max_position_embeddings", 2048), S + max_new_tokens)
@@ -691,12 +756,34 @@ class ValleyLlamaForCausalLM:
         if table is not None:
             table = table.expand(B, 4).contiguous()
         last = out.logits[:, -1, :].contiguous()
+        lp_cols, lp_done = [], []                            # per new token: its [B, 1(, n)] record; the rows already finished
+
+        def score_raw(x):
+            """lse and top-n of the raw logits, before the processors and the sampler rewrite them in place (then: a copy)"""
+            raw = torch.empty_like(x) if (table is not None or sample is not None) else None
+            _, lse, tid, tl = ops.token_logprobs(x, top=logprobs, copy=raw)
+            return (x if raw is None else raw), lse, tid, tl
+
+        def record(scored, tok):
+            raw, lse, tid, tl = scored
+            col = torch.zeros((B, 1), dtype=torch.float32, device=self.device)
+            tabs = None
+            if logprobs:
+                tabs = (torch.full((B, 1, logprobs), -1, dtype=torch.int32, device=self.device),
+                        torch.zeros((B, 1, logprobs), dtype=torch.float32, device=self.device))
+            ops.score_record(raw, lse, tok.to(torch.int32), col, None, 0, top=(tid, tl) if logprobs else None, top_tables=tabs)
+            lp_cols.append((col,) + (tabs or ()))
+            lp_done.append(finished.clone())
+
+        scored = score_raw(last) if logprobs is not None else None
         if table is not None:                                # HF's processors over each row's whole input_ids, on the device
             eos32 = None if eos is None else eos.to(torch.int32)
             hist = torch.zeros((B, cache.ctx_max), dtype=torch.int32, device=self.device)
             hist[:, :S] = input_ids.to(torch.int32)
             ops.logits_process(last, table, hist, None, S, None, eos32)
         token = pick(last, S)
+        if logprobs is not None:                             # the first token: from the prefill's last logits
+            record(scored, token)
         seq = torch.cat([input_ids, token[:, None]], dim=1)
         if B > 8 or self.model.precision == "fp32":
             use_graph = None                                 # the GEMV decode session is bf16, for <= 8 sequences
@@ -704,7 +791,8 @@ class ValleyLlamaForCausalLM:
         if use_graph is not None:
             from .decode import DecodeSession
             sess = DecodeSession(self.model.llama, cache, use_graph=bool(use_graph), sampling=sample is not None,
-                                 processors=table is not None, processor_eos=None if eos is None else eos.tolist())
+                                 processors=table is not None, processor_eos=None if eos is None else eos.tolist(),
+                                 **({} if logprobs is None else {"logprobs": logprobs}))
             if sample is not None:
                 sess.sample.copy_(sample)
             if table is not None:
@@ -731,20 +819,38 @@ class ValleyLlamaForCausalLM:
                 if bool(finished.any()) or not (greedy or sample is not None):
                     token = torch.where(finished, torch.full_like(token, pad), token)
                     sess.tok.copy_(token.to(torch.int32))
+                    if logprobs is not None and not (greedy or sample is not None):
+                        sess.record_token()                  # the step recorded its own argmax: the host's draw replaces it
+                if logprobs is not None:
+                    lp_done.append(finished.clone())
             else:
                 if mask is not None:
                     mask = torch.cat([mask.to(self.device), torch.ones((B, 1), dtype=mask.dtype, device=self.device)], dim=1)
                 out = self.forward(input_ids=token[:, None], attention_mask=mask, past_key_values=cache, use_cache=True)
                 last = out.logits[:, -1, :].contiguous()
+                scored = score_raw(last) if logprobs is not None else None
                 if table is not None:                        # the fed token joins the history at index seq_len - 1
                     ops.logits_process(last, table, hist, None, cache.seq_len, token.to(torch.int32), eos32)
                 token = torch.where(finished, torch.full_like(token, pad), pick(last, cache.seq_len))
+                if logprobs is not None:
+                    record(scored, token)
             seq = torch.cat([seq, token[:, None]], dim=1)
         ops.sk_poll_async(self.device)
         torch.cuda.current_stream().synchronize()            # the caller decodes the tokens next; a stream-K hand-off
         ops.sk_check_polled(self.device)                     # failure anywhere in this generation is reported here at the latest
         if sess is not None:
             sess.check()                                     # ticket counters / grid-barrier abort word of the decode launches
+        if logprobs is not None:                             # one read of the session's tables, after the loop
+            new = seq.shape[1] - S
+            parts = [torch.cat([c[k] for c in lp_cols], dim=1) for k in range(3 if logprobs else 1)]
+            if sess is not None:                             # columns S + 1 ..: the tokens the steps chose
+                tabs = [sess.lp_table] + list(sess.lp_top_tables or ())
+                parts = [torch.cat([p, t[:, S + 1:S + new]], dim=1) for p, t in zip(parts, tabs)]
+            done = torch.stack(lp_done, dim=1)               # [B, new]: the row had finished before this token (a pad)
+            lp_out["token_logprobs"] = torch.where(done, torch.zeros_like(parts[0]), parts[0])
+            if logprobs:
+                lp_out["top_tokens"] = torch.where(done[:, :, None], torch.full_like(parts[1], -1), parts[1])
+                lp_out["top_logprobs"] = torch.where(done[:, :, None], torch.zeros_like(parts[2]), parts[2])
         return seq
 
     def _generate_beams(self, input_ids, images, attention_mask, max_new_tokens, nb, length_penalty, early_stopping, nrs,
@@ -946,8 +1052,15 @@ class ValleyLlamaForCausalLM:
         stopping = KeywordsStoppingCriteria(['###'], tokenizer, input_ids)
         gk = {k: v for k, v in gen_kwargs.items() if k in ("max_new_tokens", "do_sample", "temperature", "eos_token_id", "num_beams",
                                                             "length_penalty", "early_stopping", "repetition_penalty",
-                                                            "no_repeat_ngram_size", "min_length", "min_new_tokens")}
-        output_ids = self.generate(input_ids=input_ids, images=images, stopping_criteria=[stopping], **gk)
+                                                            "no_repeat_ngram_size", "min_length", "min_new_tokens",
+                                                            "output_logprobs", "top_logprobs")}
+        self.last_generation = None
+        if gk.get("output_logprobs"):                        # the log-probabilities of the answer: kept on ``last_generation``
+            self.last_generation = self.generate(input_ids=input_ids, images=images, stopping_criteria=[stopping],
+                                                 return_dict_in_generate=True, **gk)
+            output_ids = self.last_generation.sequences
+        else:
+            output_ids = self.generate(input_ids=input_ids, images=images, stopping_criteria=[stopping], **gk)
         n_in = input_ids.shape[1]
         n_diff = (input_ids != output_ids[:, :n_in]).sum().item()
         if n_diff > 0:
