@@ -31,6 +31,10 @@ WQ_SOURCES = ["wq.hip"]
 # processors, whose log-sum-exp routine (beam_rows.inc) it compiles; loaded on first use
 LIB_SCORE = os.path.join(LIBDIR, "libvalley_hip_score.so")
 SCORE_SOURCES = ["score.hip"]
+# prompt-lookup speculative decoding (include/valley_hip_spec.h): the split attention of the verify step's k + 1 queries, the draft
+# lookup and the acceptance; one build serves both 16-bit storage types (dtype code, as the wq library); loaded on first use
+LIB_SPEC = os.path.join(LIBDIR, "libvalley_hip_spec.so")
+SPEC_SOURCES = ["spec.hip"]
 # the row top-K and merge that the beam and logits companions compile (beam candidates over log-softmax and over processed
 # scores), and the log-sum-exp routine the score companion shares with them
 COMPANION_SHARED = ["beam_rows.inc"]
@@ -50,8 +54,8 @@ def hipcc() -> str:
 def needs_build() -> bool:
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h)
                                                                  for h in ("valley_hip.h", "valley_hip_beam.h", "valley_hip_logits.h", "valley_hip_wq.h",
-                                                                           "valley_hip_score.h")]
-    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, LIB_BEAM, LIB_LOGITS, LIB_WQ, LIB_SCORE):
+                                                                           "valley_hip_score.h", "valley_hip_spec.h")]
+    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, LIB_BEAM, LIB_LOGITS, LIB_WQ, LIB_SCORE, LIB_SPEC):
         if not os.path.exists(lib):
             return True
         t = os.path.getmtime(lib)
@@ -70,6 +74,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(os.path.join(LIBDIR, "logits"), exist_ok=True)
     os.makedirs(os.path.join(LIBDIR, "wq"), exist_ok=True)
     os.makedirs(os.path.join(LIBDIR, "score"), exist_ok=True)
+    os.makedirs(os.path.join(LIBDIR, "spec"), exist_ok=True)
     if not force and not needs_build():
         return LIB
     variants = [(LIB, LIBDIR, [], SOURCES), (LIB_F16, os.path.join(LIBDIR, "f16"), ["-DVLY_FP16=1"], SOURCES),
@@ -98,14 +103,15 @@ def build(force: bool = False, verbose: bool = True) -> str:
             if s in AUDITED:
                 audits.append((s, odir, " ".join(flags) or "(default flags)"))
     companions = [(LIB_BEAM, "beam", BEAM_SOURCES, "valley_hip_beam.h"), (LIB_LOGITS, "logits", LOGITS_SOURCES, "valley_hip_logits.h"),
-                  (LIB_WQ, "wq", WQ_SOURCES, "valley_hip_wq.h"), (LIB_SCORE, "score", SCORE_SOURCES, "valley_hip_score.h")]
+                  (LIB_WQ, "wq", WQ_SOURCES, "valley_hip_wq.h"), (LIB_SCORE, "score", SCORE_SOURCES, "valley_hip_score.h"),
+                  (LIB_SPEC, "spec", SPEC_SOURCES, "valley_hip_spec.h")]
     for _lib, sub, units, header in companions:
         cdir = os.path.join(LIBDIR, sub)
         for s in units:
             o = os.path.join(cdir, s.replace(".hip", ".o"))
             t_dep = max([os.path.getmtime(os.path.join(CSRC, s)), os.path.getmtime(os.path.abspath(__file__)),
                          os.path.getmtime(os.path.join(HERE, "..", "include", header))] +
-                        [os.path.getmtime(os.path.join(CSRC, f)) for f in (["common.hpp"] if sub == "wq" else COMPANION_SHARED)])
+                        [os.path.getmtime(os.path.join(CSRC, f)) for f in (["common.hpp"] if sub in ("wq", "spec") else COMPANION_SHARED)])
             if force or not os.path.exists(o) or os.path.getmtime(o) < t_dep:
                 jobs.append((s, [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-save-temps=obj", "-c",
                                  os.path.join(CSRC, s), "-o", o]))

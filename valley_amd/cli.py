@@ -102,7 +102,10 @@ def main(args) -> str:
     (and vision_tower, unused: the tower comes with the checkpoint)."""
     model, tokenizer = load(args.model_name, getattr(args, "weight_quant", None))
     turns = [{"role": "system", "content": args.system_prompt or SYSTEM_TURN}, {"role": "user", "content": args.query}]
-    answer = model.completion(tokenizer, args.video_file, turns, dict(GREEDY), _require_gpu())
+    gen = dict(GREEDY)
+    if getattr(args, "prompt_lookup", None) is not None:                # HF's prompt_lookup_num_tokens: same answer, fewer decode steps
+        gen["prompt_lookup_num_tokens"] = int(args.prompt_lookup)
+    answer = model.completion(tokenizer, args.video_file, turns, gen, _require_gpu())
     print(answer)
     return answer
 
@@ -117,6 +120,9 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
         ap.add_argument(flag, type=str, default=default)
     ap.add_argument("--weight-quant", type=str, default=None, choices=["int8"],
                     help="decode with int8 projection weights (weight-only quantization; prefill stays 16-bit)")
+    ap.add_argument("--prompt-lookup", type=int, default=None, metavar="K",
+                    help="prompt-lookup speculative decoding: draft K in [1, 7] tokens per step from the prompt (greedy only; the "
+                         "answer is the same)")
     return ap.parse_args(argv)
 
 

@@ -1722,3 +1722,121 @@ def wq_gemv_rmsnorm(h, gamma, eps, q, scale, residual=None, epilogue=EPI_NONE, o
 def wq_gemv_rmsnorm_ok(M: int, K: int) -> bool:
     """Shapes vly_wq_gemv_rmsnorm takes (the caller keeps rmsnorm + wq_gemv otherwise): gemv_rmsnorm_ok's rule, 16 weights a chunk."""
     return 1 <= M <= 2 and 2048 <= K <= 6144 and K % 16 == 0
+
+
+# ---- prompt-lookup speculative decoding (libvalley_hip_spec.so, include/valley_hip_spec.h) ----------------------------------
+SPEC_MAX_QUERIES = 8     # VLY_SPEC_MAX_QUERIES
+SPEC_MAX_DRAFT = 7       # VLY_SPEC_MAX_DRAFT
+SPEC_MAX_NGRAM = 8       # VLY_SPEC_MAX_NGRAM
+SPEC_SPLITS = 4          # VLY_SPEC_SPLITS
+SPEC_PARTIAL = 132       # VLY_SPEC_PARTIAL
+
+
+def spec_scratch(B: int, S: int, heads: int, device):
+    """``(partials, arrivals)`` of ``spec_attention`` for B sequences of S queries: fp32 scratch and the zeroed tickets."""
+    return (torch.empty((B * heads * S * SPEC_SPLITS * SPEC_PARTIAL,), dtype=torch.float32, device=device),
+            torch.zeros((B * heads,), dtype=torch.int32, device=device))
+
+
+def spec_attention(qkv: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, key_valid: Optional[torch.Tensor],
+                   B: int, S: int, heads: int, past_len: int, scratch, out=None, past_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vly_spec_attention: causal attention of the S <= 8 queries of each of B sequences over the KV cache, every
+    (sequence, head) over four workgroups — ``llama_attention``'s arguments (qkv holds the ROTATED q, the caches already
+    hold positions past .. past + S - 1: what ``rope_kv`` leaves) plus ``scratch`` from ``spec_scratch``.  The row of the
+    query at position P does not depend on S or on its index in the launch, bit for bit."""
+    if not 1 <= int(S) <= SPEC_MAX_QUERIES:
+        raise ValueError(f"spec_attention: S must be in [1, {SPEC_MAX_QUERIES}], got {S}")
+    if B < 1 or heads < 1 or past_len < 0:
+        raise ValueError(f"spec_attention: B >= 1, heads >= 1 and past_len >= 0 expected, got {B}, {heads}, {past_len}")
+    if kcache.dim() != 4 or tuple(kcache.shape[:2]) != (B, heads) or kcache.shape[3] != 128 or vcache.shape != kcache.shape:
+        raise ValueError(f"spec_attention: kcache / vcache [{B}, {heads}, ctx_max, 128] expected, got {tuple(kcache.shape)} / "
+                         f"{tuple(vcache.shape)}")
+    ctx_max = kcache.shape[2]
+    if past_len + S > ctx_max:
+        raise ValueError(f"spec_attention: past_len + S = {past_len + S} exceeds the cache's {ctx_max} positions")
+    if tuple(qkv.shape) != (B * S, 3 * heads * 128):
+        raise ValueError(f"spec_attention: qkv [{B * S}, {3 * heads * 128}] expected, got {tuple(qkv.shape)}")
+    partials, arrivals = scratch
+    if partials.numel() < B * heads * S * SPEC_SPLITS * SPEC_PARTIAL or arrivals.numel() < B * heads:
+        raise ValueError("spec_attention: scratch too small for this launch (ops.spec_scratch(B, S, heads, device))")
+    kv_stride = 0
+    if key_valid is not None:
+        if key_valid.dim() != 2 or key_valid.shape[0] != B or key_valid.shape[1] < past_len + S or key_valid.stride(1) != 1:
+            raise ValueError(f"spec_attention: key_valid [{B}, >= {past_len + S}] expected, got {tuple(key_valid.shape)}")
+        if past_dev is not None and key_valid.shape[1] < ctx_max:
+            raise ValueError("spec_attention: with a device-side position key_valid must span the cache's ctx_max columns")
+        kv_stride = key_valid.stride(0)
+    if out is not None and tuple(out.shape) != (B * S, heads * 128):
+        raise ValueError(f"spec_attention: out [{B * S}, {heads * 128}] expected, got {tuple(out.shape)}")
+    from . import lib_spec
+    _chk(qkv, runtime.HALF, "qkv")
+    _chk(kcache, runtime.HALF, "kcache")
+    _chk(vcache, runtime.HALF, "vcache")
+    _chk(partials, torch.float32, "partials")
+    _chk(arrivals, torch.int32, "arrivals")
+    if key_valid is not None:
+        _chk(key_valid, torch.uint8, "key_valid", contiguous=False)
+    if past_dev is not None:
+        _chk(past_dev, torch.int32, "past_dev")
+    if out is None:
+        out = torch.empty((B * S, heads * 128), dtype=runtime.HALF, device=qkv.device)
+    _chk(out, runtime.HALF, "out")
+    rc = lib_spec.load_spec().vly_spec_attention(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), _ptr(key_valid), kv_stride,
+                                                 out.data_ptr(), B, int(S), heads, int(past_len), _ptr(past_dev), ctx_max,
+                                                 partials.data_ptr(), arrivals.data_ptr(), _wq_dtype(), _stream())
+    lib_spec.check(rc, "vly_spec_attention")
+    return out
+
+
+def _spec_k(name: str, k: int) -> int:
+    if not 1 <= int(k) <= SPEC_MAX_DRAFT:
+        raise ValueError(f"{name}: k must be in [1, {SPEC_MAX_DRAFT}], got {k}")
+    return int(k)
+
+
+def spec_draft(hist: torch.Tensor, length: Optional[torch.Tensor], len_add: int, k: int, max_ngram: int, draft: torch.Tensor,
+               draft_len: torch.Tensor, tok: torch.Tensor, eos: Optional[torch.Tensor] = None, vocab: int = 0,
+               lookup: bool = True) -> None:
+    """vly_spec_draft: HF's prompt lookup over hist int32 [ctx_max] with ``length[0] + len_add`` known tokens -> draft
+    int32 [k], draft_len int32 [1] and the verify step's tok int32 [k + 1] (the last token, then the draft).  ``eos``
+    int32 [n]: the draft is cropped in front of the first of them (and of any id outside [0, vocab) when vocab > 0).
+    ``lookup=False``: no search, tok is built from the caller's draft / draft_len."""
+    k = _spec_k("spec_draft", k)
+    if not 1 <= int(max_ngram) <= SPEC_MAX_NGRAM:
+        raise ValueError(f"spec_draft: max_ngram must be in [1, {SPEC_MAX_NGRAM}], got {max_ngram}")
+    if hist.dim() != 1 or hist.numel() < 1:
+        raise ValueError(f"spec_draft: hist [ctx_max] of one sequence expected, got {tuple(hist.shape)}")
+    if draft.numel() != k or draft_len.numel() != 1 or tok.numel() != k + 1:
+        raise ValueError(f"spec_draft: draft [{k}], draft_len [1] and tok [{k + 1}] expected, got {tuple(draft.shape)} / "
+                         f"{tuple(draft_len.shape)} / {tuple(tok.shape)}")
+    if length is None and len_add < 1:
+        raise ValueError("spec_draft: without a device-side length len_add is the length (>= 1)")
+    if length is not None and length.numel() != 1:
+        raise ValueError(f"spec_draft: length must hold 1 value, got {length.numel()}")
+    from . import lib_spec
+    for t, name in ((hist, "hist"), (draft, "draft"), (draft_len, "draft_len"), (tok, "tok")) + \
+            (((length, "length"),) if length is not None else ()) + (((eos, "eos"),) if eos is not None else ()):
+        _chk(t, torch.int32, name)
+    rc = lib_spec.load_spec().vly_spec_draft(hist.data_ptr(), hist.numel(), _ptr(length), int(len_add), k, int(max_ngram), _ptr(eos),
+                                             0 if eos is None else eos.numel(), int(vocab), int(bool(lookup)), draft.data_ptr(),
+                                             draft_len.data_ptr(), tok.data_ptr(), _stream())
+    lib_spec.check(rc, "vly_spec_draft")
+
+
+def spec_accept(am: torch.Tensor, draft: torch.Tensor, draft_len: torch.Tensor, k: int, hist: torch.Tensor, pos: torch.Tensor,
+                emit: torch.Tensor, tok: torch.Tensor, stats: torch.Tensor) -> None:
+    """vly_spec_accept, behind the argmax of the verify step's k + 1 rows (am int32 [k + 1]): n = the leading drafts that
+    equal the argmax; hist[pos + 1 .. pos + n + 1] = am[0 .. n], emit int32 [k + 2] = (n + 1, am[0 .. n], -1 ...),
+    tok[0] = am[n], stats int32 [3] += (1, draft_len, n), pos[0] += n + 1."""
+    k = _spec_k("spec_accept", k)
+    if am.numel() != k + 1 or draft.numel() != k or draft_len.numel() != 1 or emit.numel() != k + 2 or stats.numel() != 3 or \
+            pos.numel() != 1 or tok.numel() < 1 or hist.dim() != 1:
+        raise ValueError(f"spec_accept: am [{k + 1}], draft [{k}], draft_len [1], hist [ctx_max], pos [1], emit [{k + 2}], tok [>= 1] "
+                         f"and stats [3] expected")
+    from . import lib_spec
+    for t, name in ((am, "am"), (draft, "draft"), (draft_len, "draft_len"), (hist, "hist"), (pos, "pos"), (emit, "emit"),
+                    (tok, "tok"), (stats, "stats")):
+        _chk(t, torch.int32, name)
+    rc = lib_spec.load_spec().vly_spec_accept(am.data_ptr(), draft.data_ptr(), draft_len.data_ptr(), k, hist.data_ptr(), hist.numel(),
+                                              pos.data_ptr(), emit.data_ptr(), tok.data_ptr(), stats.data_ptr(), _stream())
+    lib_spec.check(rc, "vly_spec_accept")

@@ -1,0 +1,223 @@
+"""Prompt-lookup speculative decoding: one hipGraph-captured verify step for k drafted tokens of one sequence.
+
+HF's ``generate(prompt_lookup_num_tokens=k)`` proposes, as the next k tokens, the continuation of the EARLIEST earlier
+occurrence of the sequence's last n-gram, and checks them in ONE forward of k + 1 rows: row i holds the logits behind the
+i-th drafted token, so the leading drafts that equal the argmax of the row before them are tokens greedy decoding would
+have produced, and the argmax behind the last accepted draft is one more.  A step therefore emits 1 .. k + 1 tokens of
+exactly the greedy sequence for one pass over the weights (the weight-streaming GEMVs take up to 8 rows at almost the cost
+of one: DESIGN.md "speculative decoding").
+
+Everything that changes between steps lives on the device — the position, the token history the lookup reads, the draft —
+so the step (ops.spec_draft -> embedding -> L x [norm + q|k|v GEMV, ops.rope_kv of the k + 1 rows, ops.spec_attention, o GEMV,
+norm + gate|up GEMV with SwiGLU, down GEMV] -> norm + lm_head -> argmax -> ops.spec_accept) is captured once and replayed;
+the host reads one small buffer per step (how many tokens, and which)."""
+from __future__ import annotations
+
+import os
+from typing import List, Optional, Sequence
+
+import torch
+
+from . import decode as _decode
+from . import ops
+from . import runtime
+from .llama import HipKVCache, HipLlama
+
+
+def refuse_engine() -> None:
+    """The configurations a SpecDecodeSession does not run on, with the reason."""
+    if runtime.PRECISION == "fp32":
+        raise ValueError("speculative decoding needs a 16-bit engine: the fp32 engine (VALLEY_PRECISION=fp32) has no multi-row "
+                         "weight-streaming step to verify a draft with")
+    if _decode.PERSISTENT:
+        raise ValueError("speculative decoding runs the per-layer launches: unset VALLEY_DECODE_PERSISTENT (the persistent step "
+                         "is built for one query per sequence)")
+    if _decode.MERGE_IN == "oproj":
+        raise ValueError("speculative decoding merges the attention's splits inside the attention launch: unset "
+                         "VALLEY_DECODE_MERGE=oproj")
+
+
+class SpecDecodeSession:
+    def __init__(self, llama: HipLlama, cache: HipKVCache, k: int, max_ngram: int = 2, eos_ids: Optional[Sequence[int]] = None,
+                 use_graph: bool = True, lookup: bool = True):
+        """``k`` in [1, 7]: drafted tokens per step (HF's ``prompt_lookup_num_tokens``); ``max_ngram`` in [1, 8]: HF's
+        ``max_matching_ngram_size``; ``eos_ids``: a draft stops in front of the first of them.  ``lookup=False``: the step
+        does not search — the caller writes ``self.draft`` / ``self.draft_len`` before each ``step()`` (tests, and the
+        cost measurement of a step that accepts nothing).  ``VALLEY_SPEC_ATTN=prefill`` (read here) routes the attention
+        through ops.llama_attention(S = k + 1) instead of ops.spec_attention: the A/B arm and a second opinion."""
+        refuse_engine()
+        if cache.batch != 1:
+            raise ValueError(f"a SpecDecodeSession decodes one sequence: cache.batch == 1 expected, got {cache.batch}")
+        if not 1 <= int(k) <= ops.SPEC_MAX_DRAFT:
+            raise ValueError(f"k (prompt_lookup_num_tokens) must be in [1, {ops.SPEC_MAX_DRAFT}], got {k!r}")
+        if not 1 <= int(max_ngram) <= ops.SPEC_MAX_NGRAM:
+            raise ValueError(f"max_ngram (max_matching_ngram_size) must be in [1, {ops.SPEC_MAX_NGRAM}], got {max_ngram!r}")
+        if llama.heads * 128 != llama.H:
+            raise ValueError("speculative decoding needs head_dim 128")
+        self.ll, self.cache = llama, cache
+        self.k, self.M, self.max_ngram, self.lookup = int(k), int(k) + 1, int(max_ngram), bool(lookup)
+        self.wq = bool(getattr(llama, "weight_quant", None))
+        self.attn = os.environ.get("VALLEY_SPEC_ATTN", "split")
+        if self.attn not in ("split", "prefill"):
+            raise ValueError(f"VALLEY_SPEC_ATTN must be 'split' or 'prefill', got {self.attn!r}")
+        d, M, bf = llama.device, self.M, runtime.HALF
+        self.tok = torch.zeros((M,), dtype=torch.int32, device=d)          # the step's rows: the last token, then the draft
+        self.pos = torch.zeros((1,), dtype=torch.int32, device=d)          # position of tok[0] = tokens in the cache
+        self.hist = torch.full((cache.ctx_max,), -1, dtype=torch.int32, device=d)    # hist[j]: the token at cache position j
+        self.draft = torch.zeros((self.k,), dtype=torch.int32, device=d)
+        self.draft_len = torch.zeros((1,), dtype=torch.int32, device=d)
+        self.emit = torch.full((self.k + 2,), -1, dtype=torch.int32, device=d)
+        self.stats = torch.zeros((3,), dtype=torch.int32, device=d)        # steps, drafted, accepted
+        self.am = torch.zeros((M,), dtype=torch.int32, device=d)
+        self.eos = torch.tensor([int(e) for e in eos_ids], dtype=torch.int32, device=d) if eos_ids else None
+        self.h = torch.empty((M, llama.H), dtype=torch.float32, device=d)
+        self.x = torch.empty((M, llama.H), dtype=bf, device=d)
+        self.qkv = torch.empty((M, 3 * llama.H), dtype=bf, device=d)
+        self.att = torch.empty((M, llama.H), dtype=bf, device=d)
+        self.mlp = torch.empty((M, llama.I), dtype=bf, device=d)
+        self.logits = torch.empty((M, llama.Vpad), dtype=torch.float32, device=d)
+        self.scratch = ops.spec_scratch(1, M, llama.heads, d)
+        self.use_graph = use_graph
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self._gen = cache.generation
+
+    def _norm_gemv(self, gamma, w16, wq8, out, epilogue=ops.EPI_NONE):
+        """RMSNorm + projection through DecodeSession._enqueue_step's dispatch: the fused launch where it takes the shape
+        (k = 1: two rows), the int8 forms on a quantized engine."""
+        ll, M = self.ll, self.M
+        fused = _decode.FUSE_NORM and ops.gemv_rmsnorm_ok(M, ll.H)
+        if self.wq and wq8 is not None:
+            if fused and ops.wq_gemv_rmsnorm_ok(M, ll.H):
+                ops.wq_gemv_rmsnorm(self.h, gamma, ll.eps, *wq8, epilogue=epilogue, out=out)
+            else:
+                ops.rmsnorm(self.h, gamma, ll.eps, out=self.x)
+                ops.wq_gemv(self.x, *wq8, epilogue=epilogue, out=out)
+        elif fused:
+            ops.gemv_rmsnorm(self.h, gamma, ll.eps, w16, epilogue=epilogue, out=out)
+        else:
+            ops.rmsnorm(self.h, gamma, ll.eps, out=self.x)
+            ops.gemv(self.x, w16, epilogue=epilogue, out=out)
+
+    def _enqueue_step(self):
+        ll, c, M = self.ll, self.cache, self.M
+        ops.spec_draft(self.hist, self.pos, 1, self.k, self.max_ngram, self.draft, self.draft_len, self.tok, eos=self.eos, vocab=ll.V,
+                       lookup=self.lookup)
+        ops.embed_splice(self.tok, ll.embed, None, out=self.h)
+        for li in range(ll.L):
+            L = ll.layers[li]
+            self._norm_gemv(L["ln1"], L.get("w_qkv"), L.get("wq_qkv"), self.qkv)
+            # K / V of all k + 1 rows go into the cache at positions pos .. pos + k before anything is accepted.  The rows of
+            # rejected drafts then lie AT or BEHIND the new position: no later query sees them (a query at P reads keys <= P,
+            # and every position <= P has been rewritten by the step that fed its accepted token), and the next step's rope_kv
+            # overwrites them, starting at the new pos.
+            ops.rope_kv(self.qkv, c.k[li], c.v[li], ll.cos, ll.sin, 1, M, ll.heads, 0, past_dev=self.pos)
+            if self.attn == "prefill":
+                ops.llama_attention(self.qkv, c.k[li], c.v[li], c.key_valid, 1, M, ll.heads, 0, out=self.att, past_dev=self.pos)
+            else:
+                ops.spec_attention(self.qkv, c.k[li], c.v[li], c.key_valid, 1, M, ll.heads, 0, self.scratch, out=self.att,
+                                   past_dev=self.pos)
+            if self.wq:
+                ops.wq_gemv(self.att, *L["wq_o"], residual=self.h, out=self.h)
+            else:
+                ops.gemv(self.att, L["w_o"], residual=self.h, out=self.h)
+            self._norm_gemv(L["ln2"], L.get("w_gu"), L.get("wq_gu"), self.mlp, epilogue=ops.EPI_SWIGLU)
+            if self.wq:
+                ops.wq_gemv(self.mlp, *L["wq_down"], residual=self.h, out=self.h)
+            else:
+                ops.gemv(self.mlp, L["w_down"], residual=self.h, out=self.h)
+        self._norm_gemv(ll.norm, ll.lm_head, None, self.logits)
+        ops.argmax(self.logits[:, :ll.V], out=self.am)
+        ops.spec_accept(self.am, self.draft, self.draft_len, self.k, self.hist, self.pos, self.emit, self.tok, self.stats)
+
+    def _ensure_hist(self):
+        """The history spans the cache's positions (it grows with a model-sized cache)."""
+        if self.hist.numel() < self.cache.ctx_max:
+            h = torch.full((self.cache.ctx_max,), -1, dtype=torch.int32, device=self.hist.device)
+            h[:self.hist.numel()].copy_(self.hist)
+            self.hist = h
+            self._gen = None                                 # a graph holds the old history's pointer: capture again
+
+    def begin(self, first_token: torch.Tensor, prompt_ids: Optional[torch.Tensor] = None):
+        """Call after the prefill filled ``cache``: the history is the prompt's ids (``prompt_ids`` [S] or [1, S]; right-aligned
+        in front of the cache's position when the prefill spliced more positions than ids, the rest never matches) followed
+        by ``first_token``, the position is the cache's, the counters are zero."""
+        c = self.cache
+        if self.room():
+            c.reserve(c.seq_len + self.M)                    # a model-sized cache grows BEFORE the warm-up step writes its rows
+        self._ensure_hist()
+        self.hist.fill_(-1)
+        if prompt_ids is not None:
+            ids = prompt_ids.reshape(-1).to(torch.int32)[-c.seq_len:] if c.seq_len else prompt_ids.reshape(-1)[:0].to(torch.int32)
+            self.hist[c.seq_len - ids.numel():c.seq_len].copy_(ids)
+        self.hist[c.seq_len:c.seq_len + 1].copy_(first_token.reshape(-1)[:1].to(torch.int32))
+        self.pos.fill_(c.seq_len)
+        self.tok.fill_(0)
+        self.tok[:1].copy_(first_token.reshape(-1)[:1].to(torch.int32))
+        self.stats.zero_()
+        if c.key_valid is not None:
+            c.key_valid[:, c.seq_len:] = 1                   # generated positions are always attended
+        # capturing runs a warm-up step, whose rope_kv writes k + 1 rows from the position on — and the kernels clamp the position
+        # to ctx_max - (k + 1), so on a cache without that room the rows of REAL positions would be overwritten: no room, no
+        # warm-up (step() captures once there is room, and raises before anything is launched when there never is)
+        if self.use_graph and self.room() and (self.graph is None or self._gen != c.generation):
+            self._capture()
+
+    def _capture(self):
+        """DecodeSession._capture's scheme: a warm-up step on a side stream, the device-side state restored, ONE step
+        captured.  (The warm-up's K / V rows lie at and behind the position: the first real step overwrites them.)"""
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        state = [self.pos, self.tok, self.hist, self.stats, self.draft, self.draft_len, self.emit]
+        saved = [t.clone() for t in state]
+        with torch.cuda.stream(s):
+            self._enqueue_step()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        for t, t0 in zip(state, saved):
+            t.copy_(t0)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._enqueue_step()
+        self.graph = g
+        self._gen = self.cache.generation
+
+    def check(self) -> None:
+        """Raise if the split attention's ticket counters are not back at zero (a launch that did not complete)."""
+        if int(self.scratch[1].abs().sum().item()) != 0:
+            self.scratch[1].zero_()
+            raise RuntimeError("vly_spec_attention: ticket counters not at zero after a step (an attention launch did not "
+                               "complete); the step's output is invalid")
+
+    def room(self) -> bool:
+        """Whether the cache has (or can grow to) the k + 1 positions a step writes."""
+        c = self.cache
+        return c.seq_len + self.M <= (c.limit if c.growable else c.ctx_max)
+
+    def step(self) -> List[int]:
+        """One verify step: returns the 1 .. k + 1 tokens it emitted (python ints, from one small device-to-host copy) and
+        advances ``cache.seq_len`` by as many."""
+        c = self.cache
+        try:
+            c.reserve(c.seq_len + self.M)                    # grows a model-sized cache (new storage -> new graph)
+        except ValueError:
+            raise ValueError(f"KV cache: fewer than k + 1 = {self.M} positions left ({c.ctx_max - c.seq_len}); decode the rest one "
+                             "token at a time") from None
+        if c.key_valid is not None and c.key_valid.shape[1] != c.ctx_max:
+            raise RuntimeError("key_valid out of step with the cache")
+        self._ensure_hist()
+        if self.use_graph and (self.graph is None or self._gen != c.generation):
+            self._capture()
+        if self.use_graph:
+            self.graph.replay()
+        else:
+            self._enqueue_step()
+        emit = self.emit.tolist()                            # the step's one read: (n + 1, tokens, -1 ...)
+        n1 = emit[0]
+        if not 1 <= n1 <= self.M:
+            raise RuntimeError(f"vly_spec_accept reported {n1} tokens for a step of {self.M} rows")
+        c.seq_len += n1
+        return emit[1:1 + n1]
+
+    def speculation(self) -> dict:
+        s = self.stats.tolist()
+        return {"steps": s[0], "drafted": s[1], "accepted": s[2]}

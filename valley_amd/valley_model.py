@@ -644,7 +644,7 @@ class ValleyLlamaForCausalLM:
                  seed=None, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False,
                  num_return_sequences: int = 1, return_dict_in_generate: bool = False, repetition_penalty=None,
                  no_repeat_ngram_size=None, min_length=None, min_new_tokens=None, output_logprobs: bool = False,
-                 top_logprobs: int = 0, **kw):
+                 top_logprobs: int = 0, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, **kw):
         """Prefill + per-token KV decode (the loop of serve/model_worker.py:371-394; the reference's CLI
         path reaches the same through HF ``generate``, valley_model.py:432).  Greedy when not sampling or
         temperature < 1e-4, else temperature softmax + multinomial.  Decode steps run through a
@@ -672,7 +672,17 @@ class ValleyLlamaForCausalLM:
         ``compute_transition_scores(sequences, out.logits, normalize_logits=True)`` — and, with ``top_logprobs = n`` in
         [1, 20], ``top_tokens`` int32 / ``top_logprobs`` fp32 [B, new tokens, n], the n most probable ids, best first.
         Entries behind a row's end (its pad tokens) are 0, with ids -1.  Computed on the device (ops.token_logprobs /
-        ops.score_record), inside the captured step too, and read once after the loop.  Not with beams."""
+        ops.score_record), inside the captured step too, and read once after the loop.  Not with beams.
+
+        ``prompt_lookup_num_tokens = k`` in [1, 7] (HF's name; ``max_matching_ngram_size`` in [1, 8], HF's default 2):
+        prompt-lookup speculative decoding — every decode step drafts up to k tokens from the continuation of the
+        EARLIEST earlier occurrence of the sequence's last n-gram and verifies them in one k + 1-row step
+        (valley_amd.spec.SpecDecodeSession), emitting 1 .. k + 1 tokens of the greedy sequence.  The result is the one the
+        same call returns without the two arguments; ``return_dict_in_generate`` adds ``speculation`` = {"steps", "drafted",
+        "accepted"} (decode steps run, the one-token steps at the cache's end included; tokens drafted; drafts accepted).  One prompt row, greedy, no beams, no logits processors, no ``output_logprobs``, a 16-bit engine and
+        ``use_graph`` True or False — anything else is refused before a launch."""
+        spec = self._spec_args(prompt_lookup_num_tokens, max_matching_ngram_size, input_ids, do_sample, num_beams, repetition_penalty,
+                               no_repeat_ngram_size, min_length, min_new_tokens, output_logprobs or top_logprobs, use_graph)
         proc = (repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens)
         top_logprobs = 0 if top_logprobs is None else int(top_logprobs)
         if (output_logprobs or top_logprobs) and not return_dict_in_generate:
@@ -697,6 +707,10 @@ class ValleyLlamaForCausalLM:
             return SimpleNamespace(sequences=seq, sequences_scores=scores) if return_dict_in_generate else seq
         if num_return_sequences != 1:
             raise ValueError("num_return_sequences > 1 needs num_beams > 1 (sampling several sequences per prompt is not supported)")
+        if spec is not None:
+            seq, speculation = self._generate_spec(input_ids, images, attention_mask, max_new_tokens, stopping_criteria, eos_token_id,
+                                                   bool(use_graph), spec)
+            return SimpleNamespace(sequences=seq, sequences_scores=None, speculation=speculation) if return_dict_in_generate else seq
         lp_out = {} if output_logprobs else None
         seq = self._generate(input_ids, images, attention_mask, max_new_tokens, do_sample, temperature, stopping_criteria,
                              eos_token_id, use_graph, top_k, top_p, seed, proc=proc, logprobs=top_logprobs if output_logprobs else None,
@@ -704,6 +718,104 @@ class ValleyLlamaForCausalLM:
         if not return_dict_in_generate:
             return seq
         return SimpleNamespace(sequences=seq, sequences_scores=None, **(lp_out or {}))
+
+    def _spec_args(self, k, max_ngram, input_ids, do_sample, num_beams, rp, nr, ml, mn, logprobs, use_graph):
+        """``(k, max_ngram)`` of a prompt-lookup generation, or None when it was not asked for; every combination the
+        speculative step does not cover is refused here, before the model is touched."""
+        if k is None:
+            if max_ngram is not None:
+                raise ValueError("max_matching_ngram_size needs prompt_lookup_num_tokens")
+            return None
+        max_ngram = 2 if max_ngram is None else max_ngram    # HF's default
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= ops.SPEC_MAX_DRAFT:
+            raise ValueError(f"prompt_lookup_num_tokens must be an int in [1, {ops.SPEC_MAX_DRAFT}], got {k!r}")
+        if isinstance(max_ngram, bool) or not isinstance(max_ngram, int) or not 1 <= max_ngram <= ops.SPEC_MAX_NGRAM:
+            raise ValueError(f"max_matching_ngram_size must be an int in [1, {ops.SPEC_MAX_NGRAM}], got {max_ngram!r}")
+        if input_ids.dim() != 2 or input_ids.shape[0] != 1:
+            raise ValueError("prompt_lookup_num_tokens decodes one prompt row (HF's assisted decoding is batch 1 too), got "
+                             f"input_ids {tuple(input_ids.shape)}")
+        if do_sample:
+            raise ValueError("prompt_lookup_num_tokens verifies drafts against greedy decoding: do_sample=True is not supported")
+        if num_beams is not None and int(num_beams) > 1:
+            raise ValueError("prompt_lookup_num_tokens is not supported with num_beams > 1")
+        if any(a is not None for a in (rp, nr, ml, mn)):
+            raise ValueError("prompt_lookup_num_tokens is not supported with logits processors (repetition_penalty, "
+                             "no_repeat_ngram_size, min_length, min_new_tokens): they rewrite the logits a draft is checked against")
+        if logprobs:
+            raise ValueError("prompt_lookup_num_tokens is not supported with output_logprobs")
+        if use_graph is None:
+            raise ValueError("prompt_lookup_num_tokens needs the decode session: use_graph True (captured) or False (eager), not None")
+        from . import spec as _spec
+        _spec.refuse_engine()
+        return k, max_ngram
+
+    def _generate_spec(self, input_ids, images, attention_mask, max_new_tokens, stopping_criteria, eos_token_id, use_graph, spec):
+        """Greedy generation of one row through SpecDecodeSession: the tokens a step emits are appended ONE at a time, the
+        EOS test and every stopping criterion see the sequence up to that token as in ``_generate``'s loop, and whatever a
+        step emitted behind the stop or behind ``max_new_tokens`` is dropped.  When the cache has fewer than k + 1 positions
+        left, the remaining tokens come from the one-token DecodeSession; the speculative session is made (and its step
+        warmed up and captured, which writes k + 1 cache rows from the position on) only once a step of it can run, so a
+        call with ``max_new_tokens <= k`` never makes one."""
+        from .decode import DecodeSession
+        from .spec import SpecDecodeSession
+        k, max_ngram = spec
+        input_ids = input_ids.to(self.device)
+        S = input_ids.shape[1]
+        ctx = min(getattr(self.config, "max_position_embeddings", 2048), S + max_new_tokens)
+        cache = self.model.llama.new_cache(1, max(ctx, S + 1))
+        out = self.forward(input_ids=input_ids, images=images, attention_mask=attention_mask, past_key_values=cache, use_cache=True)
+        eos = None
+        if eos_token_id is not None:
+            eos = [int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id]
+        token = int(ops.argmax(out.logits[:, -1, :].contiguous())[0])
+        new = [token]
+        sess, plain, plain_steps = None, None, 0
+
+        def stopped() -> bool:
+            """``_generate``'s test before a further token: EOS, a stopping criterion on the sequence so far, the cache."""
+            if eos is not None and new[-1] in eos:
+                return True
+            if stopping_criteria is not None:
+                seq = torch.cat([input_ids, torch.tensor([new], dtype=input_ids.dtype, device=self.device)], dim=1)
+                for c in stopping_criteria:
+                    r = c(seq, None)
+                    if bool(r.to(self.device).view(-1).all()) if isinstance(r, torch.Tensor) else bool(r):
+                        return True
+            return False
+
+        done = False
+        while len(new) < max_new_tokens and not done:
+            if stopped() or cache.seq_len + 1 > cache.ctx_max:
+                break
+            if plain is None and cache.seq_len + k + 1 <= cache.ctx_max:
+                if sess is None:
+                    sess = SpecDecodeSession(self.model.llama, cache, k, max_ngram, eos_ids=eos, use_graph=use_graph)
+                    known = torch.cat([input_ids[0], torch.tensor(new[:-1], dtype=input_ids.dtype, device=self.device)])
+                    sess.begin(torch.tensor(new[-1:], device=self.device), prompt_ids=known)
+                emitted = sess.step()
+            else:                                            # the cache's last positions: one token per step
+                if plain is None:
+                    plain = DecodeSession(self.model.llama, cache, use_graph=use_graph)
+                    plain.begin(torch.tensor([new[-1]], device=self.device))
+                emitted = [int(plain.step()[0])]
+                plain_steps += 1
+            for j, t in enumerate(emitted):
+                if j and stopped():                          # (before the step's first token the loop has tested already)
+                    done = True
+                    break
+                new.append(t)
+                if len(new) == max_new_tokens:
+                    break
+        ops.sk_poll_async(self.device)
+        torch.cuda.current_stream().synchronize()
+        ops.sk_check_polled(self.device)
+        for s_ in (sess, plain):
+            if s_ is not None:
+                s_.check()
+        seq = torch.cat([input_ids, torch.tensor([new], dtype=input_ids.dtype, device=self.device)], dim=1)
+        speculation = sess.speculation() if sess is not None else {"steps": 0, "drafted": 0, "accepted": 0}
+        speculation["steps"] += plain_steps                  # decode steps of either kind: steps + accepted = tokens they emitted
+        return seq, speculation
 
     @staticmethod
     def _processor_table(proc, S: int, eos_ids, device) -> Optional[torch.Tensor]:
@@ -1053,7 +1165,8 @@ class ValleyLlamaForCausalLM:
         gk = {k: v for k, v in gen_kwargs.items() if k in ("max_new_tokens", "do_sample", "temperature", "eos_token_id", "num_beams",
                                                             "length_penalty", "early_stopping", "repetition_penalty",
                                                             "no_repeat_ngram_size", "min_length", "min_new_tokens",
-                                                            "output_logprobs", "top_logprobs")}
+                                                            "output_logprobs", "top_logprobs", "prompt_lookup_num_tokens",
+                                                            "max_matching_ngram_size")}
         self.last_generation = None
         if gk.get("output_logprobs"):                        # the log-probabilities of the answer: kept on ``last_generation``
             self.last_generation = self.generate(input_ids=input_ids, images=images, stopping_criteria=[stopping],
