@@ -27,6 +27,10 @@ LOGITS_SOURCES = ["logits.hip"]
 # 16-bit storage types (every compute entry takes the dtype code), so the main libraries' exports stay exactly valley_hip.h's
 LIB_WQ = os.path.join(LIBDIR, "libvalley_hip_wq.so")
 WQ_SOURCES = ["wq.hip"]
+# weight-only INT4 decode (include/valley_hip_w4.h): the group quantizer (one fp32 scale per 128 weights) and the 4-bit
+# weight-streaming GEMVs; a companion of the same kind as the wq library (dtype code, loaded on first use)
+LIB_W4 = os.path.join(LIBDIR, "libvalley_hip_w4.so")
+W4_SOURCES = ["w4.hip"]
 # token log-probabilities and the forward-only loss (include/valley_hip_score.h): fp32 logits and int32 ids only, like the logits
 # processors, whose log-sum-exp routine (beam_rows.inc) it compiles; loaded on first use
 LIB_SCORE = os.path.join(LIBDIR, "libvalley_hip_score.so")
@@ -54,8 +58,8 @@ def hipcc() -> str:
 def needs_build() -> bool:
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h)
                                                                  for h in ("valley_hip.h", "valley_hip_beam.h", "valley_hip_logits.h", "valley_hip_wq.h",
-                                                                           "valley_hip_score.h", "valley_hip_spec.h")]
-    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, LIB_BEAM, LIB_LOGITS, LIB_WQ, LIB_SCORE, LIB_SPEC):
+                                                                           "valley_hip_score.h", "valley_hip_spec.h", "valley_hip_w4.h")]
+    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, LIB_BEAM, LIB_LOGITS, LIB_WQ, LIB_SCORE, LIB_SPEC, LIB_W4):
         if not os.path.exists(lib):
             return True
         t = os.path.getmtime(lib)
@@ -75,6 +79,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(os.path.join(LIBDIR, "wq"), exist_ok=True)
     os.makedirs(os.path.join(LIBDIR, "score"), exist_ok=True)
     os.makedirs(os.path.join(LIBDIR, "spec"), exist_ok=True)
+    os.makedirs(os.path.join(LIBDIR, "w4"), exist_ok=True)
     if not force and not needs_build():
         return LIB
     variants = [(LIB, LIBDIR, [], SOURCES), (LIB_F16, os.path.join(LIBDIR, "f16"), ["-DVLY_FP16=1"], SOURCES),
@@ -104,14 +109,14 @@ def build(force: bool = False, verbose: bool = True) -> str:
                 audits.append((s, odir, " ".join(flags) or "(default flags)"))
     companions = [(LIB_BEAM, "beam", BEAM_SOURCES, "valley_hip_beam.h"), (LIB_LOGITS, "logits", LOGITS_SOURCES, "valley_hip_logits.h"),
                   (LIB_WQ, "wq", WQ_SOURCES, "valley_hip_wq.h"), (LIB_SCORE, "score", SCORE_SOURCES, "valley_hip_score.h"),
-                  (LIB_SPEC, "spec", SPEC_SOURCES, "valley_hip_spec.h")]
+                  (LIB_SPEC, "spec", SPEC_SOURCES, "valley_hip_spec.h"), (LIB_W4, "w4", W4_SOURCES, "valley_hip_w4.h")]
     for _lib, sub, units, header in companions:
         cdir = os.path.join(LIBDIR, sub)
         for s in units:
             o = os.path.join(cdir, s.replace(".hip", ".o"))
             t_dep = max([os.path.getmtime(os.path.join(CSRC, s)), os.path.getmtime(os.path.abspath(__file__)),
                          os.path.getmtime(os.path.join(HERE, "..", "include", header))] +
-                        [os.path.getmtime(os.path.join(CSRC, f)) for f in (["common.hpp"] if sub in ("wq", "spec") else COMPANION_SHARED)])
+                        [os.path.getmtime(os.path.join(CSRC, f)) for f in (["common.hpp"] if sub in ("wq", "spec", "w4") else COMPANION_SHARED)])
             if force or not os.path.exists(o) or os.path.getmtime(o) < t_dep:
                 jobs.append((s, [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-save-temps=obj", "-c",
                                  os.path.join(CSRC, s), "-o", o]))

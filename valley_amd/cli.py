@@ -82,7 +82,7 @@ def load_lora(path: str, device):
 
 
 def load(model_name: str, weight_quant: Optional[str] = None):
-    """-> (model on the GPU in eval mode with its token ids bound, tokenizer).  ``weight_quant="int8"``: int8 decode weights."""
+    """-> (model on the GPU in eval mode with its token ids bound, tokenizer).  ``weight_quant="int8"`` / ``"int4"``: quantized decode weights."""
     path = os.path.expanduser(model_name)
     device = _require_gpu()
     if "lora" in path:
@@ -118,8 +118,8 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
                           ("--vision-tower", None),
                           ("--system-prompt", "")):
         ap.add_argument(flag, type=str, default=default)
-    ap.add_argument("--weight-quant", type=str, default=None, choices=["int8"],
-                    help="decode with int8 projection weights (weight-only quantization; prefill stays 16-bit)")
+    ap.add_argument("--weight-quant", type=str, default=None, choices=["int8", "int4"],
+                    help="decode with int8 or group-wise int4 projection weights (weight-only quantization; prefill stays 16-bit)")
     ap.add_argument("--prompt-lookup", type=int, default=None, metavar="K",
                     help="prompt-lookup speculative decoding: draft K in [1, 7] tokens per step from the prompt (greedy only; the "
                          "answer is the same)")

@@ -78,9 +78,12 @@ class DecodeSession:
                 raise ValueError("the persistent decode step (VALLEY_DECODE_PERSISTENT=1) takes no logprobs: unset it")
             if not 0 <= int(logprobs) <= ops.SCORE_MAX_TOP:
                 raise ValueError(f"logprobs must be in [0, {ops.SCORE_MAX_TOP}] (the number of alternatives per token), got {logprobs!r}")
-        self.wq = bool(getattr(llama, "weight_quant", None))     # the four projections of every layer stream int8 weights
+        mode = getattr(llama, "weight_quant", None)
+        self.wq = bool(mode)                                     # the four projections of every layer stream int8 / int4 weights
+        # the mode's GEMVs (int8: ops.wq_*, int4: ops.w4_*), with one signature
+        self.q_gemv, self.q_gemv_rmsnorm, self.q_gemv_rmsnorm_ok = ops.quant_ops(mode)[1:] if mode else (None, None, None)
         if self.wq and (PERSISTENT or MERGE_IN == "oproj"):
-            raise ValueError("an int8-quantized engine decodes with the per-layer launches only: unset VALLEY_DECODE_PERSISTENT and "
+            raise ValueError(f"an {mode}-quantized engine decodes with the per-layer launches only: unset VALLEY_DECODE_PERSISTENT and "
                              "VALLEY_DECODE_MERGE=oproj (those forms read 16-bit weights)")
         self.per_row = per_row_positions
         self.tok = torch.zeros((B,), dtype=torch.int32, device=d)          # token fed to the next step
@@ -151,7 +154,7 @@ class DecodeSession:
         # the three norm -> projection seams as one launch each where the fused kernel takes the shape (bit-identical either way;
         # VALLEY_DECODE_FUSE_NORM=0 keeps the pairs, for A/B runs)
         fused = FUSE_NORM and ops.gemv_rmsnorm_ok(B, ll.H)
-        wq, wq_fused = self.wq, self.wq and fused and ops.wq_gemv_rmsnorm_ok(B, ll.H)
+        wq, wq_fused = self.wq, self.wq and fused and self.q_gemv_rmsnorm_ok(B, ll.H)
         # every head over four workgroups.  Merged inside the attention launch (the default) it does not depend on the o GEMV's form, so
         # three to eight rows take it too: at eight requests decode_fused_kernel's 320 workgroups of 512 threads are 1.25 rounds of one
         # workgroup per CU (23 us per layer, 15 % of the step); 1280 quarter-head workgroups stream the same K / V evenly
@@ -167,10 +170,10 @@ class DecodeSession:
         for li in range(0 if self.persistent else ll.L):
             L = ll.layers[li]
             if wq_fused:
-                ops.wq_gemv_rmsnorm(self.h, L["ln1"], ll.eps, *L["wq_qkv"], out=self.qkv)
+                self.q_gemv_rmsnorm(self.h, L["ln1"], ll.eps, *L["wq_qkv"], out=self.qkv)
             elif wq:
                 ops.rmsnorm(self.h, L["ln1"], ll.eps, out=self.x)
-                ops.wq_gemv(self.x, *L["wq_qkv"], out=self.qkv)
+                self.q_gemv(self.x, *L["wq_qkv"], out=self.qkv)
             elif fused:
                 ops.gemv_rmsnorm(self.h, L["ln1"], ll.eps, L["w_qkv"], out=self.qkv)      # input_layernorm inside the q|k|v GEMV
             else:
@@ -193,17 +196,17 @@ class DecodeSession:
             if not split:
                 self._o_proj(L)
             if wq_fused:
-                ops.wq_gemv_rmsnorm(self.h, L["ln2"], ll.eps, *L["wq_gu"], epilogue=ops.EPI_SWIGLU, out=self.mlp)
+                self.q_gemv_rmsnorm(self.h, L["ln2"], ll.eps, *L["wq_gu"], epilogue=ops.EPI_SWIGLU, out=self.mlp)
             elif wq:
                 ops.rmsnorm(self.h, L["ln2"], ll.eps, out=self.x)
-                ops.wq_gemv(self.x, *L["wq_gu"], epilogue=ops.EPI_SWIGLU, out=self.mlp)
+                self.q_gemv(self.x, *L["wq_gu"], epilogue=ops.EPI_SWIGLU, out=self.mlp)
             elif fused:
                 ops.gemv_rmsnorm(self.h, L["ln2"], ll.eps, L["w_gu"], epilogue=ops.EPI_SWIGLU, out=self.mlp)
             else:
                 ops.rmsnorm(self.h, L["ln2"], ll.eps, out=self.x)
                 ops.gemv(self.x, L["w_gu"], epilogue=ops.EPI_SWIGLU, out=self.mlp)
             if wq:
-                ops.wq_gemv(self.mlp, *L["wq_down"], residual=self.h, out=self.h)
+                self.q_gemv(self.mlp, *L["wq_down"], residual=self.h, out=self.h)
             else:
                 ops.gemv(self.mlp, L["w_down"], residual=self.h, out=self.h)
         if fused:
@@ -251,7 +254,7 @@ class DecodeSession:
 
     def _o_proj(self, L):
         if self.wq:
-            ops.wq_gemv(self.att, *L["wq_o"], residual=self.h, out=self.h)
+            self.q_gemv(self.att, *L["wq_o"], residual=self.h, out=self.h)
         else:
             ops.gemv(self.att, L["w_o"], residual=self.h, out=self.h)
 

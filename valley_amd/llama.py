@@ -21,11 +21,11 @@ import torch
 from . import ops, runtime
 
 
-WEIGHT_QUANT_MODES = ("int8",)
+WEIGHT_QUANT_MODES = ("int8", "int4")
 
 
 def parse_weight_quant(value, what: str = "weight_quant") -> Optional[str]:
-    """None / "" / "0" -> None (off), "int8" -> "int8"; anything else raises, naming the accepted values."""
+    """None / "" / "0" -> None (off), "int8" / "int4" -> itself; anything else raises, naming the accepted values."""
     if value is None or value is False:
         return None
     v = str(value).strip().lower()
@@ -43,7 +43,7 @@ def resolve_weight_quant(value, precision: str) -> Optional[str]:
         else parse_weight_quant(value)
     if mode and precision == "fp32":
         raise ValueError(f"weight_quant={mode!r} needs a 16-bit engine: precision fp32 (VALLEY_PRECISION=fp32) keeps fp32 weights and "
-                         "activations, which the int8 GEMVs do not take")
+                         "activations, which the quantized GEMVs do not take")
     return mode
 
 
@@ -126,6 +126,7 @@ class HipLlama:
                  pack_weights: Optional[bool] = None, weight_quant: Optional[str] = None):
         # weight-only INT8 decode: the one-token steps read an int8 copy of the four projections, one byte per weight
         # plus an fp32 scale per row; prefill keeps the 16-bit copies.  VALLEY_WEIGHT_QUANT=int8 or weight_quant="int8"; off by default.
+        # "int4" (§4.11): a 4-bit copy, two weights per byte plus an fp32 scale per 128 weights of a row, through the same switch.
         self.weight_quant = resolve_weight_quant(weight_quant, runtime.PRECISION)
         if hidden != heads * 128:
             raise ValueError("HIP Llama path requires head_dim == 128 (hidden = heads*128)")
@@ -157,20 +158,23 @@ class HipLlama:
             self._quantize_layers()
 
     def _quantize_layers(self):
-        done = {}                                            # one int8 copy per distinct weight tensor: aliased layers alias it too
+        quantize = ops.quant_ops(self.weight_quant)[0]
+        done = {}                                            # one quantized copy per distinct weight tensor: aliased layers alias it too
         for L in self.layers:
             for k in ("w_qkv", "w_o", "w_gu", "w_down"):
                 w = L[k]
                 key = (w.data_ptr(), tuple(w.shape))
                 if key not in done:
-                    done[key] = ops.wq_quantize(w)
+                    done[key] = quantize(w)
                 L["wq_" + k[2:]] = done[key]
 
     def quantize_weights(self, mode: str = "int8") -> "HipLlama":
-        """Switch the one-token steps to int8 weights (after the fact: the 16-bit copies stay for prefill)."""
+        """Switch the one-token steps to int8 or int4 weights (after the fact: the 16-bit copies stay for prefill)."""
         mode = resolve_weight_quant(mode or "", runtime.PRECISION)
         if mode is None:
-            raise ValueError("quantize_weights: mode must be 'int8'")
+            raise ValueError(f"quantize_weights: mode must be one of {', '.join(repr(m) for m in WEIGHT_QUANT_MODES)}")
+        if self.weight_quant and self.weight_quant != mode and any("wq_qkv" in L for L in self.layers):
+            raise ValueError(f"this engine already decodes {self.weight_quant} weights: a second mode ({mode!r}) needs a new engine")
         self.weight_quant = mode
         if self.loaded:
             self._quantize_layers()
@@ -265,7 +269,8 @@ class HipLlama:
         kv = cache.key_valid                                # uint8 [B, ctx_max] or None (row stride = ctx_max)
         nl = self.L if n_layers is None else n_layers
         fused = M > 8            # prefill: residual adds ride on the norm kernels; decode keeps the GEMV epilogue
-        wq = bool(self.weight_quant) and S == 1 and M <= 8   # the one-token step reads the int8 weights, with output_attentions too
+        wq = bool(self.weight_quant) and S == 1 and M <= 8   # the one-token step reads the quantized weights, with output_attentions too
+        qgemv = ops.quant_ops(self.weight_quant)[1] if wq else None      # (int8: ops.wq_gemv, int4: ops.w4_gemv)
         d2 = None                  # second split-K partial of the pending sub-layer output (ops.gemm2), if any
         pending = False            # ws["delta"] (+ d2) holds a sub-layer output that has not been added to h yet
         if collect is not None:
@@ -279,7 +284,7 @@ class HipLlama:
                 ops.rmsnorm(h, L["ln1"], self.eps, out=ws["x"])
             if attn is not None:                            # output_attentions: the unfused sequence leaves the rotated q in qkv
                 if wq:
-                    ops.wq_gemv(ws["x"], *L["wq_qkv"], out=ws["qkv"])
+                    qgemv(ws["x"], *L["wq_qkv"], out=ws["qkv"])
                 else:
                     ops.gemm(ws["x"], W["w_qkv"], out=ws["qkv"])
                 ops.rope_kv(ws["qkv"], cache.k[li], cache.v[li], self.cos, self.sin, B, S, self.heads, past)
@@ -287,7 +292,7 @@ class HipLlama:
                 attn.append(ops.attention_probs(ws["qkv"], cache.k[li], kv, B, S, self.heads, past))
             elif S == 1:                                    # one-token step: RoPE + append + attention fused
                 if wq:
-                    ops.wq_gemv(ws["x"], *L["wq_qkv"], out=ws["qkv"])
+                    qgemv(ws["x"], *L["wq_qkv"], out=ws["qkv"])
                 else:
                     ops.gemm(ws["x"], W["w_qkv"], out=ws["qkv"])
                 ops.decode_attention(ws["qkv"], cache.k[li], cache.v[li], self.cos, self.sin, kv, B, self.heads, past,
@@ -304,20 +309,20 @@ class HipLlama:
                 d2 = ws["delta2"] if ops.gemm2(ws["att"], W["w_o"], ws["delta"], ws["delta2"]) == 2 else None
                 ops.add_norm(h, ws["delta"], L["ln2"], None, self.eps, out=ws["x"], rms=True, delta2=d2)
             elif wq:
-                ops.wq_gemv(ws["att"], *L["wq_o"], residual=h, out=h)
+                qgemv(ws["att"], *L["wq_o"], residual=h, out=h)
                 ops.rmsnorm(h, L["ln2"], self.eps, out=ws["x"])
             else:
                 ops.gemm(ws["att"], L["w_o"], residual=h, out=h)
                 ops.rmsnorm(h, L["ln2"], self.eps, out=ws["x"])
             if wq:
-                ops.wq_gemv(ws["x"], *L["wq_gu"], epilogue=ops.EPI_SWIGLU, out=ws["mlp"])
+                qgemv(ws["x"], *L["wq_gu"], epilogue=ops.EPI_SWIGLU, out=ws["mlp"])
             else:
                 ops.gemm(ws["x"], W["w_gu"], epilogue=ops.EPI_SWIGLU, out=ws["mlp"])
             if fused:
                 d2 = ws["delta2"] if ops.gemm2(ws["mlp"], W["w_down"], ws["delta"], ws["delta2"]) == 2 else None
                 pending = True
             elif wq:
-                ops.wq_gemv(ws["mlp"], *L["wq_down"], residual=h, out=h)
+                qgemv(ws["mlp"], *L["wq_down"], residual=h, out=h)
             else:
                 ops.gemm(ws["mlp"], L["w_down"], residual=h, out=h)
             if collect is not None and li + 1 < nl:

@@ -1724,6 +1724,101 @@ def wq_gemv_rmsnorm_ok(M: int, K: int) -> bool:
     return 1 <= M <= 2 and 2048 <= K <= 6144 and K % 16 == 0
 
 
+# ---- weight-only INT4 decode (libvalley_hip_w4.so, include/valley_hip_w4.h) ------------------------------------------------
+W4_GROUP = 128           # VLY_W4_GROUP: consecutive k of a row that share one scale
+
+
+def _w4_chk(t, dtype, name, contiguous=True):
+    """_chk for the w4 entries: a wrong dtype is a ValleyHipError too (the library has no kernel for it)."""
+    try:
+        _chk(t, dtype, name, contiguous)
+    except TypeError as e:
+        raise _lib.ValleyHipError(str(e)) from None
+
+
+def w4_quantize(w: torch.Tensor):
+    """Group-wise symmetric 4-bit quantization of a 16-bit weight [N, K], K % 128 == 0: -> (packed uint8 [N, K / 2] in the layout
+    of valley_hip_w4.h, scale fp32 [N, K / 128]) with s = amax / 7 per group of 128, q = clamp(rint(w / s), -7, 7); an all-zero
+    group gives s = 1, q = 0."""
+    from . import lib_w4
+    _w4_chk(w, runtime.HALF, "w", contiguous=False)
+    if w.dim() != 2 or w.stride(1) != 1:
+        raise ValueError(f"w4_quantize: a [N, K] weight with unit column stride expected, got {tuple(w.shape)}")
+    N, K = w.shape
+    q = torch.empty((N, K // 2), dtype=torch.uint8, device=w.device)
+    scale = torch.empty((N, max(K // W4_GROUP, 1)), dtype=torch.float32, device=w.device)
+    rc = lib_w4.load_w4().vly_w4_quantize_rows(w.data_ptr(), w.stride(0), N, K, _wq_dtype(), q.data_ptr(), scale.data_ptr(), _stream())
+    lib_w4.check(rc, "vly_w4_quantize_rows")
+    return q, scale
+
+
+def _w4_common(M, K, q, scale, residual, epilogue, out_dtype, out, device):
+    """Argument checks shared by w4_gemv and w4_gemv_rmsnorm -> (out, out code)."""
+    _w4_chk(q, torch.uint8, "q", contiguous=False)
+    _w4_chk(scale, torch.float32, "scale")
+    assert q.dim() == 2 and q.stride(1) == 1 and q.shape[1] * 2 == K, (q.shape, K)
+    N = q.shape[0]
+    if K % W4_GROUP == 0:                                       # (another K is the library's to refuse, by name)
+        assert tuple(scale.shape) == (N, K // W4_GROUP), (scale.shape, N, K)
+    No = N // 2 if epilogue == EPI_SWIGLU else N
+    if out is None:
+        out = torch.empty((M, No), dtype=runtime.HALF if out_dtype is None else out_dtype, device=device)
+    else:
+        if out.dtype not in (runtime.HALF, torch.float32):
+            raise _lib.ValleyHipError(f"out: expected {runtime.HALF} or torch.float32, got {out.dtype}")
+        _w4_chk(out, out.dtype, "out", contiguous=False)
+        assert tuple(out.shape) == (M, No) and out.stride(1) == 1, (out.shape, (M, No))
+    if residual is not None:
+        _w4_chk(residual, torch.float32, "residual", contiguous=False)
+        assert tuple(residual.shape) == (M, N) and residual.stride(1) == 1
+    return out, (OUT_F32 if out.dtype == torch.float32 else OUT_BF16)
+
+
+def w4_gemv(a, q, scale, residual=None, epilogue=EPI_NONE, out_dtype=None, out=None):
+    """vly_w4_gemv: out[M <= 8, N'] = epi(sum_g scale[n, g] * (a[M, g] @ q[N, g]^T)) + residual over the 4-bit weights
+    ``(q, scale)`` of ``w4_quantize``; EPI_NONE (16-bit or fp32 out) or EPI_SWIGLU (16-bit out)."""
+    from . import lib_w4
+    _w4_chk(a, runtime.HALF, "a", contiguous=False)
+    assert a.dim() == 2 and a.stride(1) == 1, a.shape
+    M, K = a.shape
+    out, od = _w4_common(M, K, q, scale, residual, epilogue, out_dtype, out, a.device)
+    rc = lib_w4.load_w4().vly_w4_gemv(a.data_ptr(), a.stride(0), q.data_ptr(), q.stride(0), scale.data_ptr(), _ptr(residual),
+                                      residual.stride(0) if residual is not None else 0, out.data_ptr(), out.stride(0), M, q.shape[0], K,
+                                      epilogue, od, _wq_dtype(), _stream())
+    lib_w4.check(rc, "vly_w4_gemv")
+    return out
+
+
+def w4_gemv_rmsnorm(h, gamma, eps, q, scale, residual=None, epilogue=EPI_NONE, out_dtype=None, out=None):
+    """vly_w4_gemv_rmsnorm: w4_gemv(rmsnorm(h, gamma, eps), q, scale, ...) in one launch (M <= 2 rows, 2048 <= K <= 6144) —
+    bit-identical to the pair."""
+    from . import lib_w4
+    _w4_chk(h, torch.float32, "h", contiguous=False)
+    _w4_chk(gamma, torch.float32, "gamma")
+    assert h.dim() == 2 and h.stride(1) == 1 and h.shape[1] == gamma.numel(), (h.shape, gamma.shape)
+    M, K = h.shape
+    out, od = _w4_common(M, K, q, scale, residual, epilogue, out_dtype, out, h.device)
+    rc = lib_w4.load_w4().vly_w4_gemv_rmsnorm(h.data_ptr(), h.stride(0), gamma.data_ptr(), eps, q.data_ptr(), q.stride(0),
+                                              scale.data_ptr(), _ptr(residual), residual.stride(0) if residual is not None else 0,
+                                              out.data_ptr(), out.stride(0), M, q.shape[0], K, epilogue, od, _wq_dtype(), _stream())
+    lib_w4.check(rc, "vly_w4_gemv_rmsnorm")
+    return out
+
+
+def w4_gemv_rmsnorm_ok(M: int, K: int) -> bool:
+    """Shapes vly_w4_gemv_rmsnorm takes (the caller keeps rmsnorm + w4_gemv otherwise)."""
+    return 1 <= M <= 2 and 2048 <= K <= 6144 and K % W4_GROUP == 0
+
+
+def quant_ops(mode):
+    """(quantize, gemv, gemv_rmsnorm, gemv_rmsnorm_ok) of a weight_quant mode: what a quantized engine's one-token steps call."""
+    if mode == "int8":
+        return wq_quantize, wq_gemv, wq_gemv_rmsnorm, wq_gemv_rmsnorm_ok
+    if mode == "int4":
+        return w4_quantize, w4_gemv, w4_gemv_rmsnorm, w4_gemv_rmsnorm_ok
+    raise ValueError(f"no quantized GEMVs for weight_quant={mode!r}")
+
+
 # ---- prompt-lookup speculative decoding (libvalley_hip_spec.so, include/valley_hip_spec.h) ----------------------------------
 SPEC_MAX_QUERIES = 8     # VLY_SPEC_MAX_QUERIES
 SPEC_MAX_DRAFT = 7       # VLY_SPEC_MAX_DRAFT

@@ -56,7 +56,9 @@ class SpecDecodeSession:
             raise ValueError("speculative decoding needs head_dim 128")
         self.ll, self.cache = llama, cache
         self.k, self.M, self.max_ngram, self.lookup = int(k), int(k) + 1, int(max_ngram), bool(lookup)
-        self.wq = bool(getattr(llama, "weight_quant", None))
+        mode = getattr(llama, "weight_quant", None)
+        self.wq = bool(mode)
+        self.q_gemv, self.q_gemv_rmsnorm, self.q_gemv_rmsnorm_ok = ops.quant_ops(mode)[1:] if mode else (None, None, None)
         self.attn = os.environ.get("VALLEY_SPEC_ATTN", "split")
         if self.attn not in ("split", "prefill"):
             raise ValueError(f"VALLEY_SPEC_ATTN must be 'split' or 'prefill', got {self.attn!r}")
@@ -87,11 +89,11 @@ class SpecDecodeSession:
         ll, M = self.ll, self.M
         fused = _decode.FUSE_NORM and ops.gemv_rmsnorm_ok(M, ll.H)
         if self.wq and wq8 is not None:
-            if fused and ops.wq_gemv_rmsnorm_ok(M, ll.H):
-                ops.wq_gemv_rmsnorm(self.h, gamma, ll.eps, *wq8, epilogue=epilogue, out=out)
+            if fused and self.q_gemv_rmsnorm_ok(M, ll.H):
+                self.q_gemv_rmsnorm(self.h, gamma, ll.eps, *wq8, epilogue=epilogue, out=out)
             else:
                 ops.rmsnorm(self.h, gamma, ll.eps, out=self.x)
-                ops.wq_gemv(self.x, *wq8, epilogue=epilogue, out=out)
+                self.q_gemv(self.x, *wq8, epilogue=epilogue, out=out)
         elif fused:
             ops.gemv_rmsnorm(self.h, gamma, ll.eps, w16, epilogue=epilogue, out=out)
         else:
@@ -117,12 +119,12 @@ class SpecDecodeSession:
                 ops.spec_attention(self.qkv, c.k[li], c.v[li], c.key_valid, 1, M, ll.heads, 0, self.scratch, out=self.att,
                                    past_dev=self.pos)
             if self.wq:
-                ops.wq_gemv(self.att, *L["wq_o"], residual=self.h, out=self.h)
+                self.q_gemv(self.att, *L["wq_o"], residual=self.h, out=self.h)
             else:
                 ops.gemv(self.att, L["w_o"], residual=self.h, out=self.h)
             self._norm_gemv(L["ln2"], L.get("w_gu"), L.get("wq_gu"), self.mlp, epilogue=ops.EPI_SWIGLU)
             if self.wq:
-                ops.wq_gemv(self.mlp, *L["wq_down"], residual=self.h, out=self.h)
+                self.q_gemv(self.mlp, *L["wq_down"], residual=self.h, out=self.h)
             else:
                 ops.gemv(self.mlp, L["w_down"], residual=self.h, out=self.h)
         self._norm_gemv(ll.norm, ll.lm_head, None, self.logits)

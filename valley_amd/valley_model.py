@@ -533,7 +533,8 @@ class ValleyLlamaForCausalLM:
     @classmethod
     def from_pretrained(cls, path: str, torch_dtype=None, device="cuda:0", weight_quant=None, **kw):
         """Sharded HF checkpoint directory (config.json + *.safetensors / pytorch_model-*.bin).  ``weight_quant="int8"``: the decode
-        steps read int8 projection weights (README "Weight-only INT8 decode")."""
+        steps read int8 projection weights (README "Weight-only INT8 decode"); ``"int4"``: 4-bit ones with a scale per 128 weights
+        (README "Weight-only INT4 decode")."""
         from .checkpoint import load_valley_checkpoint
         config, sd = load_valley_checkpoint(path, ValleyConfig)
         config.mm_vision_tower_name = getattr(config, "mm_vision_tower", None)
@@ -553,7 +554,7 @@ class ValleyLlamaForCausalLM:
         return model
 
     def quantize_decode_weights(self, mode: str = "int8"):
-        """After the fact: the one-token decode steps of this model read int8 copies of the Llama projections from here on
+        """After the fact: the one-token decode steps of this model read int8 (or, ``mode="int4"``, 4-bit) copies of the Llama projections from here on
         (prefill, lm_head, embeddings, norms and the vision tower keep their weights)."""
         from .llama import resolve_weight_quant
         self.model.llama.quantize_weights(resolve_weight_quant(mode or "", self.model.precision))
