@@ -42,6 +42,8 @@ SPEC_SOURCES = ["spec.hip"]
 # the row top-K and merge that the beam and logits companions compile (beam candidates over log-softmax and over processed
 # scores), and the log-sum-exp routine the score companion shares with them
 COMPANION_SHARED = ["beam_rows.inc"]
+# the headers the other companions compile instead: qgemv.hpp is the GEMV skeleton the two weight-only formats share
+COMPANION_DEPS = {"wq": ["common.hpp", "qgemv.hpp"], "w4": ["common.hpp", "qgemv.hpp"], "spec": ["common.hpp"]}
 SOURCES = ["capi.hip", "gemm_bf16.hip", "gemm_p32.hip", "gemm_p16.hip", "gemm_streamk.hip", "norm_elementwise.hip", "attention.hip", "temporal_delta.hip", "preprocess.hip", "gemv_bf16.hip", "precise_f32.hip", "gemm_skinny.hip", "decode_step.hip", "sampling.hip"]
 
 
@@ -116,7 +118,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
             o = os.path.join(cdir, s.replace(".hip", ".o"))
             t_dep = max([os.path.getmtime(os.path.join(CSRC, s)), os.path.getmtime(os.path.abspath(__file__)),
                          os.path.getmtime(os.path.join(HERE, "..", "include", header))] +
-                        [os.path.getmtime(os.path.join(CSRC, f)) for f in (["common.hpp"] if sub in ("wq", "spec", "w4") else COMPANION_SHARED)])
+                        [os.path.getmtime(os.path.join(CSRC, f)) for f in COMPANION_DEPS.get(sub, COMPANION_SHARED)])
             if force or not os.path.exists(o) or os.path.getmtime(o) < t_dep:
                 jobs.append((s, [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-save-temps=obj", "-c",
                                  os.path.join(CSRC, s), "-o", o]))

@@ -5,9 +5,10 @@ libvalley_hip.so.  Every wrapper validates dtype/device/contiguity and raises on
 error codes."""
 from __future__ import annotations
 
+import importlib
 import os
 import threading
-from typing import Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -1648,166 +1649,152 @@ def nll_mean(target_lp: torch.Tensor, targets: torch.Tensor, V: int):
     return loss, count
 
 
-# ---- weight-only INT8 decode (libvalley_hip_wq.so, include/valley_hip_wq.h) ------------------------------------------------
+# ---- weight-only decode: INT8 rows (libvalley_hip_wq.so, include/valley_hip_wq.h) and INT4 groups (libvalley_hip_w4.so,
+# include/valley_hip_w4.h).  One implementation, parameterised by what the formats do not share; each library loads on its
+# format's first call and never for the other's. ----
+W4_GROUP = 128           # VLY_W4_GROUP: consecutive k of a row that share one scale
+
+
+class _QuantFormat(NamedTuple):
+    """What one weight-only format brings to the shared implementation below."""
+    prefix: str                 # binding module lib_<prefix> with load_<prefix>(); entries vly_<prefix>_*
+    q_dtype: torch.dtype        # the packed weight's dtype
+    k_mult: int                 # vly_<prefix>_gemv_rmsnorm takes K % k_mult == 0
+    dtype_error: type           # what a tensor of the wrong dtype raises
+    alloc_shapes: Callable      # (N, K) -> (q shape, scale shape) of the quantizer's outputs
+    shapes_ok: Callable         # (q, scale, K) -> do q and scale fit K
+
+    def call(self, name, *args):
+        """vly_<prefix>_<name>(*args) from the format's library, loaded on first use; a non-zero return raises."""
+        mod = importlib.import_module(f"{__package__}.lib_{self.prefix}")
+        full = f"vly_{self.prefix}_{name}"
+        mod.check(getattr(getattr(mod, f"load_{self.prefix}")(), full)(*args), full)
+
+    def chk(self, t, dtype, name, contiguous=True):
+        """_chk with the format's error for a wrong dtype."""
+        try:
+            _chk(t, dtype, name, contiguous)
+        except TypeError as e:
+            raise self.dtype_error(str(e)) from None
+
+
+_INT8 = _QuantFormat("wq", torch.int8, 16, TypeError,
+                     lambda N, K: ((N, K), (N,)),
+                     lambda q, scale, K: q.shape[1] == K and scale.numel() == q.shape[0])
+# a wrong dtype is a ValleyHipError too (the library has no kernel for it); a K off the group size is the library's to refuse, by name
+_INT4 = _QuantFormat("w4", torch.uint8, W4_GROUP, _lib.ValleyHipError,
+                     lambda N, K: ((N, K // 2), (N, max(K // W4_GROUP, 1))),
+                     lambda q, scale, K: q.shape[1] * 2 == K and (K % W4_GROUP != 0 or tuple(scale.shape) == (q.shape[0], K // W4_GROUP)))
+
+
 def _wq_dtype() -> int:
     return 1 if runtime.HALF == torch.float16 else 0          # the codes of vly_storage_dtype
 
 
-def wq_quantize(w: torch.Tensor):
-    """Per-row symmetric int8 quantization of a 16-bit weight [N, K]: -> (q int8 [N, K], scale fp32 [N]) with
-    s = amax / 127, q = clamp(rint(w / s), -127, 127); an all-zero row gives s = 1, q = 0."""
-    from . import lib_wq
-    _chk(w, runtime.HALF, "w", contiguous=False)
+def _q_quantize(fmt, who, w):
+    fmt.chk(w, runtime.HALF, "w", contiguous=False)
     if w.dim() != 2 or w.stride(1) != 1:
-        raise ValueError(f"wq_quantize: a [N, K] weight with unit column stride expected, got {tuple(w.shape)}")
+        raise ValueError(f"{who}: a [N, K] weight with unit column stride expected, got {tuple(w.shape)}")
     N, K = w.shape
-    q = torch.empty((N, K), dtype=torch.int8, device=w.device)
-    scale = torch.empty((N,), dtype=torch.float32, device=w.device)
-    rc = lib_wq.load_wq().vly_wq_quantize_rows(w.data_ptr(), w.stride(0), N, K, _wq_dtype(), q.data_ptr(), scale.data_ptr(), _stream())
-    lib_wq.check(rc, "vly_wq_quantize_rows")
+    q_shape, scale_shape = fmt.alloc_shapes(N, K)
+    q = torch.empty(q_shape, dtype=fmt.q_dtype, device=w.device)
+    scale = torch.empty(scale_shape, dtype=torch.float32, device=w.device)
+    fmt.call("quantize_rows", w.data_ptr(), w.stride(0), N, K, _wq_dtype(), q.data_ptr(), scale.data_ptr(), _stream())
     return q, scale
 
 
-def _wq_common(M, K, q, scale, residual, epilogue, out_dtype, out, device):
-    """Argument checks shared by wq_gemv and wq_gemv_rmsnorm -> (out, out code)."""
-    _chk(q, torch.int8, "q", contiguous=False)
-    _chk(scale, torch.float32, "scale")
-    assert q.dim() == 2 and q.stride(1) == 1 and q.shape[1] == K and scale.numel() == q.shape[0], (q.shape, K, scale.shape)
+def _q_common(fmt, M, K, q, scale, residual, epilogue, out_dtype, out, device):
+    """Argument checks shared by the GEMV and the fused-norm GEMV -> (out, out code)."""
+    fmt.chk(q, fmt.q_dtype, "q", contiguous=False)
+    fmt.chk(scale, torch.float32, "scale")
+    assert q.dim() == 2 and q.stride(1) == 1 and fmt.shapes_ok(q, scale, K), (q.shape, K, scale.shape)
     N = q.shape[0]
     No = N // 2 if epilogue == EPI_SWIGLU else N
     if out is None:
         out = torch.empty((M, No), dtype=runtime.HALF if out_dtype is None else out_dtype, device=device)
     else:
         if out.dtype not in (runtime.HALF, torch.float32):
-            raise TypeError(f"out: expected {runtime.HALF} or torch.float32, got {out.dtype}")
-        _chk(out, out.dtype, "out", contiguous=False)
+            raise fmt.dtype_error(f"out: expected {runtime.HALF} or torch.float32, got {out.dtype}")
+        fmt.chk(out, out.dtype, "out", contiguous=False)
         assert tuple(out.shape) == (M, No) and out.stride(1) == 1, (out.shape, (M, No))
     if residual is not None:
-        _chk(residual, torch.float32, "residual", contiguous=False)
+        fmt.chk(residual, torch.float32, "residual", contiguous=False)
         assert tuple(residual.shape) == (M, N) and residual.stride(1) == 1
     return out, (OUT_F32 if out.dtype == torch.float32 else OUT_BF16)
+
+
+def _q_gemv(fmt, a, q, scale, residual, epilogue, out_dtype, out):
+    fmt.chk(a, runtime.HALF, "a", contiguous=False)
+    assert a.dim() == 2 and a.stride(1) == 1, a.shape
+    M, K = a.shape
+    out, od = _q_common(fmt, M, K, q, scale, residual, epilogue, out_dtype, out, a.device)
+    fmt.call("gemv", a.data_ptr(), a.stride(0), q.data_ptr(), q.stride(0), scale.data_ptr(), _ptr(residual),
+             residual.stride(0) if residual is not None else 0, out.data_ptr(), out.stride(0), M, q.shape[0], K, epilogue, od,
+             _wq_dtype(), _stream())
+    return out
+
+
+def _q_gemv_rmsnorm(fmt, h, gamma, eps, q, scale, residual, epilogue, out_dtype, out):
+    fmt.chk(h, torch.float32, "h", contiguous=False)
+    fmt.chk(gamma, torch.float32, "gamma")
+    assert h.dim() == 2 and h.stride(1) == 1 and h.shape[1] == gamma.numel(), (h.shape, gamma.shape)
+    M, K = h.shape
+    out, od = _q_common(fmt, M, K, q, scale, residual, epilogue, out_dtype, out, h.device)
+    fmt.call("gemv_rmsnorm", h.data_ptr(), h.stride(0), gamma.data_ptr(), eps, q.data_ptr(), q.stride(0), scale.data_ptr(),
+             _ptr(residual), residual.stride(0) if residual is not None else 0, out.data_ptr(), out.stride(0), M, q.shape[0], K,
+             epilogue, od, _wq_dtype(), _stream())
+    return out
+
+
+def _q_gemv_rmsnorm_ok(fmt, M, K):
+    return 1 <= M <= 2 and 2048 <= K <= 6144 and K % fmt.k_mult == 0
+
+
+def wq_quantize(w: torch.Tensor):
+    """Per-row symmetric int8 quantization of a 16-bit weight [N, K]: -> (q int8 [N, K], scale fp32 [N]) with
+    s = amax / 127, q = clamp(rint(w / s), -127, 127); an all-zero row gives s = 1, q = 0."""
+    return _q_quantize(_INT8, "wq_quantize", w)
 
 
 def wq_gemv(a, q, scale, residual=None, epilogue=EPI_NONE, out_dtype=None, out=None):
     """vly_wq_gemv: out[M <= 8, N'] = epi(scale[n] * (a[M, K] @ q[N, K]^T)) + residual over int8 weights ``(q, scale)`` of
     ``wq_quantize``; EPI_NONE (16-bit or fp32 out) or EPI_SWIGLU (16-bit out)."""
-    from . import lib_wq
-    _chk(a, runtime.HALF, "a", contiguous=False)
-    assert a.dim() == 2 and a.stride(1) == 1, a.shape
-    M, K = a.shape
-    out, od = _wq_common(M, K, q, scale, residual, epilogue, out_dtype, out, a.device)
-    rc = lib_wq.load_wq().vly_wq_gemv(a.data_ptr(), a.stride(0), q.data_ptr(), q.stride(0), scale.data_ptr(), _ptr(residual),
-                                      residual.stride(0) if residual is not None else 0, out.data_ptr(), out.stride(0), M, q.shape[0], K,
-                                      epilogue, od, _wq_dtype(), _stream())
-    lib_wq.check(rc, "vly_wq_gemv")
-    return out
+    return _q_gemv(_INT8, a, q, scale, residual, epilogue, out_dtype, out)
 
 
 def wq_gemv_rmsnorm(h, gamma, eps, q, scale, residual=None, epilogue=EPI_NONE, out_dtype=None, out=None):
     """vly_wq_gemv_rmsnorm: wq_gemv(rmsnorm(h, gamma, eps), q, scale, ...) in one launch (M <= 2 rows, 2048 <= K <= 6144) —
     bit-identical to the pair."""
-    from . import lib_wq
-    _chk(h, torch.float32, "h", contiguous=False)
-    _chk(gamma, torch.float32, "gamma")
-    assert h.dim() == 2 and h.stride(1) == 1 and h.shape[1] == gamma.numel(), (h.shape, gamma.shape)
-    M, K = h.shape
-    out, od = _wq_common(M, K, q, scale, residual, epilogue, out_dtype, out, h.device)
-    rc = lib_wq.load_wq().vly_wq_gemv_rmsnorm(h.data_ptr(), h.stride(0), gamma.data_ptr(), eps, q.data_ptr(), q.stride(0),
-                                              scale.data_ptr(), _ptr(residual), residual.stride(0) if residual is not None else 0,
-                                              out.data_ptr(), out.stride(0), M, q.shape[0], K, epilogue, od, _wq_dtype(), _stream())
-    lib_wq.check(rc, "vly_wq_gemv_rmsnorm")
-    return out
+    return _q_gemv_rmsnorm(_INT8, h, gamma, eps, q, scale, residual, epilogue, out_dtype, out)
 
 
 def wq_gemv_rmsnorm_ok(M: int, K: int) -> bool:
     """Shapes vly_wq_gemv_rmsnorm takes (the caller keeps rmsnorm + wq_gemv otherwise): gemv_rmsnorm_ok's rule, 16 weights a chunk."""
-    return 1 <= M <= 2 and 2048 <= K <= 6144 and K % 16 == 0
-
-
-# ---- weight-only INT4 decode (libvalley_hip_w4.so, include/valley_hip_w4.h) ------------------------------------------------
-W4_GROUP = 128           # VLY_W4_GROUP: consecutive k of a row that share one scale
-
-
-def _w4_chk(t, dtype, name, contiguous=True):
-    """_chk for the w4 entries: a wrong dtype is a ValleyHipError too (the library has no kernel for it)."""
-    try:
-        _chk(t, dtype, name, contiguous)
-    except TypeError as e:
-        raise _lib.ValleyHipError(str(e)) from None
+    return _q_gemv_rmsnorm_ok(_INT8, M, K)
 
 
 def w4_quantize(w: torch.Tensor):
     """Group-wise symmetric 4-bit quantization of a 16-bit weight [N, K], K % 128 == 0: -> (packed uint8 [N, K / 2] in the layout
     of valley_hip_w4.h, scale fp32 [N, K / 128]) with s = amax / 7 per group of 128, q = clamp(rint(w / s), -7, 7); an all-zero
     group gives s = 1, q = 0."""
-    from . import lib_w4
-    _w4_chk(w, runtime.HALF, "w", contiguous=False)
-    if w.dim() != 2 or w.stride(1) != 1:
-        raise ValueError(f"w4_quantize: a [N, K] weight with unit column stride expected, got {tuple(w.shape)}")
-    N, K = w.shape
-    q = torch.empty((N, K // 2), dtype=torch.uint8, device=w.device)
-    scale = torch.empty((N, max(K // W4_GROUP, 1)), dtype=torch.float32, device=w.device)
-    rc = lib_w4.load_w4().vly_w4_quantize_rows(w.data_ptr(), w.stride(0), N, K, _wq_dtype(), q.data_ptr(), scale.data_ptr(), _stream())
-    lib_w4.check(rc, "vly_w4_quantize_rows")
-    return q, scale
-
-
-def _w4_common(M, K, q, scale, residual, epilogue, out_dtype, out, device):
-    """Argument checks shared by w4_gemv and w4_gemv_rmsnorm -> (out, out code)."""
-    _w4_chk(q, torch.uint8, "q", contiguous=False)
-    _w4_chk(scale, torch.float32, "scale")
-    assert q.dim() == 2 and q.stride(1) == 1 and q.shape[1] * 2 == K, (q.shape, K)
-    N = q.shape[0]
-    if K % W4_GROUP == 0:                                       # (another K is the library's to refuse, by name)
-        assert tuple(scale.shape) == (N, K // W4_GROUP), (scale.shape, N, K)
-    No = N // 2 if epilogue == EPI_SWIGLU else N
-    if out is None:
-        out = torch.empty((M, No), dtype=runtime.HALF if out_dtype is None else out_dtype, device=device)
-    else:
-        if out.dtype not in (runtime.HALF, torch.float32):
-            raise _lib.ValleyHipError(f"out: expected {runtime.HALF} or torch.float32, got {out.dtype}")
-        _w4_chk(out, out.dtype, "out", contiguous=False)
-        assert tuple(out.shape) == (M, No) and out.stride(1) == 1, (out.shape, (M, No))
-    if residual is not None:
-        _w4_chk(residual, torch.float32, "residual", contiguous=False)
-        assert tuple(residual.shape) == (M, N) and residual.stride(1) == 1
-    return out, (OUT_F32 if out.dtype == torch.float32 else OUT_BF16)
+    return _q_quantize(_INT4, "w4_quantize", w)
 
 
 def w4_gemv(a, q, scale, residual=None, epilogue=EPI_NONE, out_dtype=None, out=None):
     """vly_w4_gemv: out[M <= 8, N'] = epi(sum_g scale[n, g] * (a[M, g] @ q[N, g]^T)) + residual over the 4-bit weights
     ``(q, scale)`` of ``w4_quantize``; EPI_NONE (16-bit or fp32 out) or EPI_SWIGLU (16-bit out)."""
-    from . import lib_w4
-    _w4_chk(a, runtime.HALF, "a", contiguous=False)
-    assert a.dim() == 2 and a.stride(1) == 1, a.shape
-    M, K = a.shape
-    out, od = _w4_common(M, K, q, scale, residual, epilogue, out_dtype, out, a.device)
-    rc = lib_w4.load_w4().vly_w4_gemv(a.data_ptr(), a.stride(0), q.data_ptr(), q.stride(0), scale.data_ptr(), _ptr(residual),
-                                      residual.stride(0) if residual is not None else 0, out.data_ptr(), out.stride(0), M, q.shape[0], K,
-                                      epilogue, od, _wq_dtype(), _stream())
-    lib_w4.check(rc, "vly_w4_gemv")
-    return out
+    return _q_gemv(_INT4, a, q, scale, residual, epilogue, out_dtype, out)
 
 
 def w4_gemv_rmsnorm(h, gamma, eps, q, scale, residual=None, epilogue=EPI_NONE, out_dtype=None, out=None):
     """vly_w4_gemv_rmsnorm: w4_gemv(rmsnorm(h, gamma, eps), q, scale, ...) in one launch (M <= 2 rows, 2048 <= K <= 6144) —
     bit-identical to the pair."""
-    from . import lib_w4
-    _w4_chk(h, torch.float32, "h", contiguous=False)
-    _w4_chk(gamma, torch.float32, "gamma")
-    assert h.dim() == 2 and h.stride(1) == 1 and h.shape[1] == gamma.numel(), (h.shape, gamma.shape)
-    M, K = h.shape
-    out, od = _w4_common(M, K, q, scale, residual, epilogue, out_dtype, out, h.device)
-    rc = lib_w4.load_w4().vly_w4_gemv_rmsnorm(h.data_ptr(), h.stride(0), gamma.data_ptr(), eps, q.data_ptr(), q.stride(0),
-                                              scale.data_ptr(), _ptr(residual), residual.stride(0) if residual is not None else 0,
-                                              out.data_ptr(), out.stride(0), M, q.shape[0], K, epilogue, od, _wq_dtype(), _stream())
-    lib_w4.check(rc, "vly_w4_gemv_rmsnorm")
-    return out
+    return _q_gemv_rmsnorm(_INT4, h, gamma, eps, q, scale, residual, epilogue, out_dtype, out)
 
 
 def w4_gemv_rmsnorm_ok(M: int, K: int) -> bool:
     """Shapes vly_w4_gemv_rmsnorm takes (the caller keeps rmsnorm + w4_gemv otherwise)."""
-    return 1 <= M <= 2 and 2048 <= K <= 6144 and K % W4_GROUP == 0
+    return _q_gemv_rmsnorm_ok(_INT4, M, K)
 
 
 def quant_ops(mode):
