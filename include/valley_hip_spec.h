@@ -9,6 +9,12 @@
  * 0 on success, -22 (EINVAL) on bad arguments (message in vly_spec_last_error(), thread-local), -(1000 + hipError_t) if a
  * launch failed.  Every value that changes from one step to the next (position, history, draft, tokens) is read on the
  * device, so the launches can live in a captured graph and replay with new values.
+ *
+ * Greedy or seeded sampling.  vly_spec_accept compares the drafts with whatever ids `am` holds: the argmax of the verify step's
+ * k + 1 logit rows, or — under seeded sampling — their DRAWS, row j drawn by vly_argmax with the counter of the position it
+ * would occupy (pos + j + 1).  A draw is a function of (logits, seed, counter) alone, so the accepted tokens are the ones plain
+ * seeded decoding draws.  The counters come from vly_spec_counters in the companion libvalley_hip_spec_sample.so
+ * (valley_hip_spec_sample.h); this library's entries, signatures and ABI version are unchanged by it.
  */
 #ifndef VALLEY_HIP_SPEC_H
 #define VALLEY_HIP_SPEC_H
@@ -66,7 +72,7 @@ int vly_spec_attention(const void *qkv, const void *kcache, const void *vcache, 
 int vly_spec_draft(const int32_t *hist, int ctx_max, const int32_t *len_dev, int len_add, int k, int max_ngram, const int32_t *eos,
                    int n_eos, int vocab, int lookup, int32_t *draft, int32_t *draft_len, int32_t *tok, void *stream);
 
-/* Behind vly_argmax over the k + 1 logit rows (am int32 [k+1]): with pos = pos_dev[0], n = the number of leading
+/* Behind vly_argmax over the k + 1 logit rows (am int32 [k+1]: the argmax, or the seeded draws): with pos = pos_dev[0], n = the number of leading
  * i < dl with draft[i] == am[i], where dl = draft_len[0] clamped to [0, min(k, ctx_max - (pos + 1))] — vly_spec_draft's
  * clamp, so only rows that were fed a draft are compared.  Then:
  *   hist[pos+1 .. pos+n+1] = am[0 .. n] (only the columns inside [0, ctx_max)),

@@ -39,11 +39,15 @@ SCORE_SOURCES = ["score.hip"]
 # lookup and the acceptance; one build serves both 16-bit storage types (dtype code, as the wq library); loaded on first use
 LIB_SPEC = os.path.join(LIBDIR, "libvalley_hip_spec.so")
 SPEC_SOURCES = ["spec.hip"]
+# the draw counters of a verify step under seeded sampling (include/valley_hip_spec_sample.h): int32 only; a companion of its
+# own so that the spec library's exports and ABI version stay what they were; loaded by a sampled speculative generation only
+LIB_SPEC_SAMPLE = os.path.join(LIBDIR, "libvalley_hip_spec_sample.so")
+SPEC_SAMPLE_SOURCES = ["spec_sample.hip"]
 # the row top-K and merge that the beam and logits companions compile (beam candidates over log-softmax and over processed
 # scores), and the log-sum-exp routine the score companion shares with them
 COMPANION_SHARED = ["beam_rows.inc"]
 # the headers the other companions compile instead: qgemv.hpp is the GEMV skeleton the two weight-only formats share
-COMPANION_DEPS = {"wq": ["common.hpp", "qgemv.hpp"], "w4": ["common.hpp", "qgemv.hpp"], "spec": ["common.hpp"]}
+COMPANION_DEPS = {"wq": ["common.hpp", "qgemv.hpp"], "w4": ["common.hpp", "qgemv.hpp"], "spec": ["common.hpp"], "spec_sample": []}
 SOURCES = ["capi.hip", "gemm_bf16.hip", "gemm_p32.hip", "gemm_p16.hip", "gemm_streamk.hip", "norm_elementwise.hip", "attention.hip", "temporal_delta.hip", "preprocess.hip", "gemv_bf16.hip", "precise_f32.hip", "gemm_skinny.hip", "decode_step.hip", "sampling.hip"]
 
 
@@ -60,8 +64,9 @@ def hipcc() -> str:
 def needs_build() -> bool:
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h)
                                                                  for h in ("valley_hip.h", "valley_hip_beam.h", "valley_hip_logits.h", "valley_hip_wq.h",
-                                                                           "valley_hip_score.h", "valley_hip_spec.h", "valley_hip_w4.h")]
-    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, LIB_BEAM, LIB_LOGITS, LIB_WQ, LIB_SCORE, LIB_SPEC, LIB_W4):
+                                                                           "valley_hip_score.h", "valley_hip_spec.h", "valley_hip_w4.h",
+                                                                           "valley_hip_spec_sample.h")]
+    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, LIB_BEAM, LIB_LOGITS, LIB_WQ, LIB_SCORE, LIB_SPEC, LIB_W4, LIB_SPEC_SAMPLE):
         if not os.path.exists(lib):
             return True
         t = os.path.getmtime(lib)
@@ -82,6 +87,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(os.path.join(LIBDIR, "score"), exist_ok=True)
     os.makedirs(os.path.join(LIBDIR, "spec"), exist_ok=True)
     os.makedirs(os.path.join(LIBDIR, "w4"), exist_ok=True)
+    os.makedirs(os.path.join(LIBDIR, "spec_sample"), exist_ok=True)
     if not force and not needs_build():
         return LIB
     variants = [(LIB, LIBDIR, [], SOURCES), (LIB_F16, os.path.join(LIBDIR, "f16"), ["-DVLY_FP16=1"], SOURCES),
@@ -111,7 +117,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
                 audits.append((s, odir, " ".join(flags) or "(default flags)"))
     companions = [(LIB_BEAM, "beam", BEAM_SOURCES, "valley_hip_beam.h"), (LIB_LOGITS, "logits", LOGITS_SOURCES, "valley_hip_logits.h"),
                   (LIB_WQ, "wq", WQ_SOURCES, "valley_hip_wq.h"), (LIB_SCORE, "score", SCORE_SOURCES, "valley_hip_score.h"),
-                  (LIB_SPEC, "spec", SPEC_SOURCES, "valley_hip_spec.h"), (LIB_W4, "w4", W4_SOURCES, "valley_hip_w4.h")]
+                  (LIB_SPEC, "spec", SPEC_SOURCES, "valley_hip_spec.h"), (LIB_W4, "w4", W4_SOURCES, "valley_hip_w4.h"),
+                  (LIB_SPEC_SAMPLE, "spec_sample", SPEC_SAMPLE_SOURCES, "valley_hip_spec_sample.h")]
     for _lib, sub, units, header in companions:
         cdir = os.path.join(LIBDIR, sub)
         for s in units:

@@ -37,6 +37,32 @@ SYSTEM_TURN = " ".join((
 ))
 
 GREEDY = {"do_sample": False, "temperature": 0.2, "max_new_tokens": 1024}
+_PROCESS_SEED = None
+
+
+def process_seed() -> int:
+    """The seed of this process's sampled speculative generations when none was given: drawn once from torch's generator (as
+    ``generate`` does for ``top_k`` without a seed) and printed to stderr, so that the run can be repeated with ``--seed``."""
+    global _PROCESS_SEED
+    if _PROCESS_SEED is None:
+        import sys
+        _PROCESS_SEED = int(torch.randint(0, 1 << 62, (1,)))
+        print(f"prompt-lookup under sampling: seed {_PROCESS_SEED} (repeat this run with --seed {_PROCESS_SEED})", file=sys.stderr)
+    return _PROCESS_SEED
+
+
+def lookup_kwargs(prompt_lookup=None, seed=None, sampled: bool = False) -> dict:
+    """The ``generate`` arguments of ``--prompt-lookup K`` / ``--seed N``: nothing when neither is given.  A sampled entry
+    point that speculates needs a seed (a draft is verified against plain SEEDED decoding): the given one, else this
+    process's."""
+    kw = {}
+    if prompt_lookup is not None:
+        kw["prompt_lookup_num_tokens"] = int(prompt_lookup)
+        if sampled and seed is None:
+            seed = process_seed()
+    if seed is not None:
+        kw["seed"] = int(seed)
+    return kw
 
 
 
@@ -102,9 +128,10 @@ def main(args) -> str:
     (and vision_tower, unused: the tower comes with the checkpoint)."""
     model, tokenizer = load(args.model_name, getattr(args, "weight_quant", None))
     turns = [{"role": "system", "content": args.system_prompt or SYSTEM_TURN}, {"role": "user", "content": args.query}]
-    gen = dict(GREEDY)
-    if getattr(args, "prompt_lookup", None) is not None:                # HF's prompt_lookup_num_tokens: same answer, fewer decode steps
-        gen["prompt_lookup_num_tokens"] = int(args.prompt_lookup)
+    sampled = bool(getattr(args, "sample", False))                      # the reference's sampled settings (T = 0.2) instead of greedy
+    gen = dict(SAMPLED if sampled else GREEDY)
+    # HF's prompt_lookup_num_tokens: same answer, fewer decode steps (sampled: the same answer as the same seed without it)
+    gen.update(lookup_kwargs(getattr(args, "prompt_lookup", None), getattr(args, "seed", None), sampled))
     answer = model.completion(tokenizer, args.video_file, turns, gen, _require_gpu())
     print(answer)
     return answer
@@ -121,8 +148,13 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap.add_argument("--weight-quant", type=str, default=None, choices=["int8", "int4"],
                     help="decode with int8 or group-wise int4 projection weights (weight-only quantization; prefill stays 16-bit)")
     ap.add_argument("--prompt-lookup", type=int, default=None, metavar="K",
-                    help="prompt-lookup speculative decoding: draft K in [1, 7] tokens per step from the prompt (greedy only; the "
-                         "answer is the same)")
+                    help="prompt-lookup speculative decoding: draft K in [1, 7] tokens per step from the prompt (the answer is the "
+                         "same; with --sample: the same as the same --seed gives without it)")
+    ap.add_argument("--sample", action="store_true",
+                    help="decode with the reference's sampled settings (do_sample, temperature 0.2) instead of greedy")
+    ap.add_argument("--seed", type=int, default=None, metavar="N",
+                    help="seed of the on-device draws of --sample; with --prompt-lookup a missing seed is drawn once and printed "
+                         "to stderr")
     return ap.parse_args(argv)
 
 
@@ -140,10 +172,13 @@ def v2_message(query: Optional[str] = None, system_prompt: Optional[str] = None)
             {"role": "user", "content": query or f"{DEFAULT_VIDEO_TOKEN} Describe the video concisely."}]
 
 
-def main_v2(video_file: str, model_path: str = VALLEY2_7B):
-    """run_valley_llamma_v2.py as a function: Valley2-7b, the fixed 4-turn message, sampled decoding (T = 0.2)."""
+def main_v2(video_file: str, model_path: str = VALLEY2_7B, prompt_lookup: Optional[int] = None, seed: Optional[int] = None):
+    """run_valley_llamma_v2.py as a function: Valley2-7b, the fixed 4-turn message, sampled decoding (T = 0.2).
+    ``prompt_lookup`` / ``seed``: speculative decoding of the seeded sequence (``lookup_kwargs``)."""
     model, tokenizer = load(model_path)
-    return model.completion(tokenizer, video_file, v2_message(), dict(SAMPLED), _require_gpu())
+    gen = dict(SAMPLED)
+    gen.update(lookup_kwargs(prompt_lookup, seed, sampled=True))
+    return model.completion(tokenizer, video_file, v2_message(), gen, _require_gpu())
 
 
 # ---- valley/inference/run_valley_conv.py ---------------------------------------------------------------------------------
@@ -172,14 +207,17 @@ def conv_user_turn(qs: str, n_frames: int, image_token_len: int = 256, use_im_st
     return qs + "\n" + DEFAULT_IMAGE_PATCH_TOKEN * image_token_len
 
 
-def assistant_out(model, conv, tokenizer, input_ids, image_tensor) -> str:
+def assistant_out(model, conv, tokenizer, input_ids, image_tensor, prompt_lookup: Optional[int] = None,
+                  seed: Optional[int] = None) -> str:
     """run_valley_conv.py:54-92: sampled generate (T = 0.2, up to 1024 tokens, stop on '###'), strip the role prefixes,
-    cut at the separator, newlines removed."""
+    cut at the separator, newlines removed.  ``prompt_lookup`` / ``seed``: speculative decoding of the seeded sequence
+    (``lookup_kwargs``); with neither, ``generate`` gets exactly the reference's arguments."""
     from .video import KeywordsStoppingCriteria
     stopping = KeywordsStoppingCriteria(["###"], tokenizer, input_ids)
     with torch.inference_mode():
         output_ids = model.generate(input_ids, images=image_tensor.unsqueeze(0), do_sample=True, temperature=0.2,
-                                    max_new_tokens=1024, stopping_criteria=[stopping])
+                                    max_new_tokens=1024, stopping_criteria=[stopping],
+                                    **lookup_kwargs(prompt_lookup, seed, sampled=True))
     n_in = input_ids.shape[1]
     n_diff = (input_ids != output_ids[:, :n_in]).sum().item()
     if n_diff > 0:
@@ -240,7 +278,8 @@ def conv_inference(args, read_line=input, emit=print):
                 conv.has_video = True
             conv.append_message(conv.roles[0], qs)
             input_ids = torch.as_tensor(tokenizer([conv.get_prompt()]).input_ids).to(device)
-            answer = assistant_out(model, conv, tokenizer, input_ids, image_tensor)
+            answer = assistant_out(model, conv, tokenizer, input_ids, image_tensor, getattr(args, "prompt_lookup", None),
+                                   getattr(args, "seed", None))
             conv.append_message(conv.roles[1], answer)
             emit("Assistant: " + answer.strip() + "\n")
         except Exception as e:  # noqa: BLE001 - the reference prints the error as the assistant's turn and keeps going
@@ -254,4 +293,13 @@ def conv_parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap.add_argument("--video_file", type=str, required=False, default="")
     ap.add_argument("--vision-tower", type=str, default=None)
     ap.add_argument("--conv-mode", type=str, default="v1")
+    ap.add_argument("--prompt-lookup", type=int, default=None, metavar="K",
+                    help="prompt-lookup speculative decoding: draft K in [1, 7] tokens per step from the dialogue so far (the "
+                         "answers are the ones the same --seed gives without it)")
+    ap.add_argument("--seed", type=int, default=None, metavar="N",
+                    help="seed of the on-device draws; with --prompt-lookup a missing seed is drawn once and printed to stderr")
     return ap.parse_args(argv)
+
+
+if __name__ == "__main__":
+    main(parse_args())

@@ -1922,3 +1922,24 @@ def spec_accept(am: torch.Tensor, draft: torch.Tensor, draft_len: torch.Tensor, 
     rc = lib_spec.load_spec().vly_spec_accept(am.data_ptr(), draft.data_ptr(), draft_len.data_ptr(), k, hist.data_ptr(), hist.numel(),
                                               pos.data_ptr(), emit.data_ptr(), tok.data_ptr(), stats.data_ptr(), _stream())
     lib_spec.check(rc, "vly_spec_accept")
+
+
+def spec_counters(pos: torch.Tensor, k: int, ctx_max: int, out: torch.Tensor) -> torch.Tensor:
+    """vly_spec_counters (libvalley_hip_spec_sample.so): out int32 [k + 1] = pos[0] + (0 .. k), the position clamped to
+    [0, ctx_max - (k + 1)] as the verify step's other kernels clamp it.  With ``argmax(..., ctr=out, ctr_add=1)`` over the
+    step's k + 1 logit rows, row j draws the token of sequence index pos + j + 1: what the one-token step draws there."""
+    k = _spec_k("spec_counters", k)
+    if not isinstance(pos, torch.Tensor) or pos.dtype != torch.int32 or pos.numel() != 1:
+        raise ValueError(f"spec_counters: pos must be an int32 tensor of 1 element, got "
+                         f"{getattr(pos, 'dtype', type(pos))} {tuple(getattr(pos, 'shape', ()))}")
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or out.dim() != 1 or out.numel() != k + 1:
+        raise ValueError(f"spec_counters: out must be int32 [{k + 1}], got {getattr(out, 'dtype', type(out))} "
+                         f"{tuple(getattr(out, 'shape', ()))}")
+    if isinstance(ctx_max, bool) or int(ctx_max) < k + 1:
+        raise ValueError(f"spec_counters: ctx_max must be >= k + 1 = {k + 1}, got {ctx_max}")
+    from . import lib_spec_sample
+    _chk(pos, torch.int32, "pos")
+    _chk(out, torch.int32, "out")
+    rc = lib_spec_sample.load_spec_sample().vly_spec_counters(pos.data_ptr(), k, int(ctx_max), out.data_ptr(), _stream())
+    lib_spec_sample.check(rc, "vly_spec_counters")
+    return out

@@ -10,7 +10,12 @@ of one: DESIGN.md "speculative decoding").
 Everything that changes between steps lives on the device — the position, the token history the lookup reads, the draft —
 so the step (ops.spec_draft -> embedding -> L x [norm + q|k|v GEMV, ops.rope_kv of the k + 1 rows, ops.spec_attention, o GEMV,
 norm + gate|up GEMV with SwiGLU, down GEMV] -> norm + lm_head -> argmax -> ops.spec_accept) is captured once and replayed;
-the host reads one small buffer per step (how many tokens, and which)."""
+the host reads one small buffer per step (how many tokens, and which).
+
+Under seeded sampling (``sampling=True``) "argmax" reads "draw": row i draws, with the counter of the position it would occupy,
+the token plain seeded decoding draws there (a draw is a function of the logits, the seed and that counter), so the leading
+drafts that equal the draws of the rows before them are tokens of exactly the seed's sequence (ops.spec_counters -> ops.argmax
+with per-row counters in place of the plain argmax; DESIGN.md "seeded sampling")."""
 from __future__ import annotations
 
 import os
@@ -39,12 +44,16 @@ def refuse_engine() -> None:
 
 class SpecDecodeSession:
     def __init__(self, llama: HipLlama, cache: HipKVCache, k: int, max_ngram: int = 2, eos_ids: Optional[Sequence[int]] = None,
-                 use_graph: bool = True, lookup: bool = True):
+                 use_graph: bool = True, lookup: bool = True, sampling: bool = False):
         """``k`` in [1, 7]: drafted tokens per step (HF's ``prompt_lookup_num_tokens``); ``max_ngram`` in [1, 8]: HF's
         ``max_matching_ngram_size``; ``eos_ids``: a draft stops in front of the first of them.  ``lookup=False``: the step
         does not search — the caller writes ``self.draft`` / ``self.draft_len`` before each ``step()`` (tests, and the
         cost measurement of a step that accepts nothing).  ``VALLEY_SPEC_ATTN=prefill`` (read here) routes the attention
-        through ops.llama_attention(S = k + 1) instead of ops.spec_attention: the A/B arm and a second opinion."""
+        through ops.llama_attention(S = k + 1) instead of ops.spec_attention: the A/B arm and a second opinion.
+        ``sampling``: the step DRAWS its k + 1 tokens instead of taking the argmax, with the parameters in ``self.sample`` (int32
+        [k + 1, 6]: the sequence's ops.sampling_rows row, replicated by the caller; all rows greedy until written).  Row j draws
+        with the counter of the token it would emit, ``pos + j + 1`` (``self.ctr``, written by ops.spec_counters inside the step),
+        which is what DecodeSession(sampling=True) draws with at that position: the same seed gives the same sequence."""
         refuse_engine()
         if cache.batch != 1:
             raise ValueError(f"a SpecDecodeSession decodes one sequence: cache.batch == 1 expected, got {cache.batch}")
@@ -71,6 +80,8 @@ class SpecDecodeSession:
         self.emit = torch.full((self.k + 2,), -1, dtype=torch.int32, device=d)
         self.stats = torch.zeros((3,), dtype=torch.int32, device=d)        # steps, drafted, accepted
         self.am = torch.zeros((M,), dtype=torch.int32, device=d)
+        self.sample = ops.sampling_rows([0.0] * M, device=d) if sampling else None
+        self.ctr = torch.zeros((M,), dtype=torch.int32, device=d) if sampling else None
         self.eos = torch.tensor([int(e) for e in eos_ids], dtype=torch.int32, device=d) if eos_ids else None
         self.h = torch.empty((M, llama.H), dtype=torch.float32, device=d)
         self.x = torch.empty((M, llama.H), dtype=bf, device=d)
@@ -128,7 +139,11 @@ class SpecDecodeSession:
             else:
                 ops.gemv(self.mlp, L["w_down"], residual=self.h, out=self.h)
         self._norm_gemv(ll.norm, ll.lm_head, None, self.logits)
-        ops.argmax(self.logits[:, :ll.V], out=self.am)
+        if self.sample is None:
+            ops.argmax(self.logits[:, :ll.V], out=self.am)
+        else:                                                # row j: the draw of sequence index pos + j + 1
+            ops.spec_counters(self.pos, self.k, c.ctx_max, self.ctr)
+            ops.argmax(self.logits[:, :ll.V], sampling=self.sample, ctr=self.ctr, ctr_add=1, out=self.am)
         ops.spec_accept(self.am, self.draft, self.draft_len, self.k, self.hist, self.pos, self.emit, self.tok, self.stats)
 
     def _ensure_hist(self):
@@ -169,7 +184,8 @@ class SpecDecodeSession:
         captured.  (The warm-up's K / V rows lie at and behind the position: the first real step overwrites them.)"""
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
-        state = [self.pos, self.tok, self.hist, self.stats, self.draft, self.draft_len, self.emit]
+        state = [self.pos, self.tok, self.hist, self.stats, self.draft, self.draft_len, self.emit] + \
+            ([self.ctr] if self.ctr is not None else [])
         saved = [t.clone() for t in state]
         with torch.cuda.stream(s):
             self._enqueue_step()

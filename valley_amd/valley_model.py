@@ -680,10 +680,14 @@ class ValleyLlamaForCausalLM:
         EARLIEST earlier occurrence of the sequence's last n-gram and verifies them in one k + 1-row step
         (valley_amd.spec.SpecDecodeSession), emitting 1 .. k + 1 tokens of the greedy sequence.  The result is the one the
         same call returns without the two arguments; ``return_dict_in_generate`` adds ``speculation`` = {"steps", "drafted",
-        "accepted"} (decode steps run, the one-token steps at the cache's end included; tokens drafted; drafts accepted).  One prompt row, greedy, no beams, no logits processors, no ``output_logprobs``, a 16-bit engine and
-        ``use_graph`` True or False — anything else is refused before a launch."""
+        "accepted"} (decode steps run, the one-token steps at the cache's end included; tokens drafted; drafts accepted).  One prompt row, no beams, no logits processors, no ``output_logprobs``, a 16-bit engine and
+        ``use_graph`` True or False — anything else is refused before a launch.  Greedy, or ``do_sample=True`` WITH ``seed``
+        (one int, or a list of one): row j of the verify step then draws with the counter of the position it would occupy,
+        the leading drafts that equal those draws are accepted, and the sequence is token for token the one the same
+        seeded call returns without the two arguments.  ``do_sample=True`` without a seed is refused: there is no sequence
+        to agree with."""
         spec = self._spec_args(prompt_lookup_num_tokens, max_matching_ngram_size, input_ids, do_sample, num_beams, repetition_penalty,
-                               no_repeat_ngram_size, min_length, min_new_tokens, output_logprobs or top_logprobs, use_graph)
+                               no_repeat_ngram_size, min_length, min_new_tokens, output_logprobs or top_logprobs, use_graph, seed)
         proc = (repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens)
         top_logprobs = 0 if top_logprobs is None else int(top_logprobs)
         if (output_logprobs or top_logprobs) and not return_dict_in_generate:
@@ -710,7 +714,7 @@ class ValleyLlamaForCausalLM:
             raise ValueError("num_return_sequences > 1 needs num_beams > 1 (sampling several sequences per prompt is not supported)")
         if spec is not None:
             seq, speculation = self._generate_spec(input_ids, images, attention_mask, max_new_tokens, stopping_criteria, eos_token_id,
-                                                   bool(use_graph), spec)
+                                                   bool(use_graph), spec, do_sample, temperature, top_k, top_p)
             return SimpleNamespace(sequences=seq, sequences_scores=None, speculation=speculation) if return_dict_in_generate else seq
         lp_out = {} if output_logprobs else None
         seq = self._generate(input_ids, images, attention_mask, max_new_tokens, do_sample, temperature, stopping_criteria,
@@ -720,9 +724,11 @@ class ValleyLlamaForCausalLM:
             return seq
         return SimpleNamespace(sequences=seq, sequences_scores=None, **(lp_out or {}))
 
-    def _spec_args(self, k, max_ngram, input_ids, do_sample, num_beams, rp, nr, ml, mn, logprobs, use_graph):
-        """``(k, max_ngram)`` of a prompt-lookup generation, or None when it was not asked for; every combination the
-        speculative step does not cover is refused here, before the model is touched."""
+    def _spec_args(self, k, max_ngram, input_ids, do_sample, num_beams, rp, nr, ml, mn, logprobs, use_graph, seed=None):
+        """``(k, max_ngram, seed)`` of a prompt-lookup generation, or None when it was not asked for; every combination the
+        speculative step does not cover is refused here, before the model is touched.  ``seed`` is the one row's seed (an
+        int, or a list of one) and is what admits ``do_sample=True``: the verify step checks a draft against the draws of
+        plain SEEDED decoding, which only a seed pins."""
         if k is None:
             if max_ngram is not None:
                 raise ValueError("max_matching_ngram_size needs prompt_lookup_num_tokens")
@@ -735,8 +741,16 @@ class ValleyLlamaForCausalLM:
         if input_ids.dim() != 2 or input_ids.shape[0] != 1:
             raise ValueError("prompt_lookup_num_tokens decodes one prompt row (HF's assisted decoding is batch 1 too), got "
                              f"input_ids {tuple(input_ids.shape)}")
-        if do_sample:
-            raise ValueError("prompt_lookup_num_tokens verifies drafts against greedy decoding: do_sample=True is not supported")
+        if isinstance(seed, (list, tuple)):
+            if len(seed) != 1:
+                raise ValueError(f"prompt_lookup_num_tokens decodes one prompt row: one seed expected, got {len(seed)}")
+            seed = seed[0]
+        if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64):
+            raise ValueError(f"seed must be an int in [0, 2^64) (or a list of one), got {seed!r}")
+        if do_sample and seed is None:
+            raise ValueError("prompt_lookup_num_tokens with do_sample=True needs seed=: a draft is verified against the draws of "
+                             "plain seeded decoding (the same seed gives the same sequence), and without a seed there is no "
+                             "sequence to agree with")
         if num_beams is not None and int(num_beams) > 1:
             raise ValueError("prompt_lookup_num_tokens is not supported with num_beams > 1")
         if any(a is not None for a in (rp, nr, ml, mn)):
@@ -748,18 +762,27 @@ class ValleyLlamaForCausalLM:
             raise ValueError("prompt_lookup_num_tokens needs the decode session: use_graph True (captured) or False (eager), not None")
         from . import spec as _spec
         _spec.refuse_engine()
-        return k, max_ngram
+        return k, max_ngram, seed
 
-    def _generate_spec(self, input_ids, images, attention_mask, max_new_tokens, stopping_criteria, eos_token_id, use_graph, spec):
-        """Greedy generation of one row through SpecDecodeSession: the tokens a step emits are appended ONE at a time, the
+    def _generate_spec(self, input_ids, images, attention_mask, max_new_tokens, stopping_criteria, eos_token_id, use_graph, spec,
+                       do_sample=False, temperature=1.0, top_k=None, top_p=None):
+        """Generation of one row through SpecDecodeSession: the tokens a step emits are appended ONE at a time, the
         EOS test and every stopping criterion see the sequence up to that token as in ``_generate``'s loop, and whatever a
         step emitted behind the stop or behind ``max_new_tokens`` is dropped.  When the cache has fewer than k + 1 positions
         left, the remaining tokens come from the one-token DecodeSession; the speculative session is made (and its step
         warmed up and captured, which writes k + 1 cache rows from the position on) only once a step of it can run, so a
-        call with ``max_new_tokens <= k`` never makes one."""
+        call with ``max_new_tokens <= k`` never makes one.
+
+        Greedy, or — ``do_sample`` with a temperature of at least ops.GREEDY_T, which ``_spec_args`` admits with a seed only —
+        seeded sampling: the first token is ``_generate``'s draw from the prefill's last logits, both sessions are made with
+        ``sampling=True`` and hold the row's parameters, and every draw is keyed by (seed, index of the drawn token), so the
+        sequence is plain seeded decoding's whichever session, and whichever row of a verify step, drew a token."""
         from .decode import DecodeSession
         from .spec import SpecDecodeSession
-        k, max_ngram = spec
+        k, max_ngram, seed = spec
+        sample = None                                        # the row's parameters of the on-device draw (checked before the prefill)
+        if do_sample and temperature >= ops.GREEDY_T:
+            sample = ops.sampling_rows(float(temperature), 0 if top_k is None else top_k, 1.0 if top_p is None else top_p, [seed])
         input_ids = input_ids.to(self.device)
         S = input_ids.shape[1]
         ctx = min(getattr(self.config, "max_position_embeddings", 2048), S + max_new_tokens)
@@ -768,7 +791,11 @@ class ValleyLlamaForCausalLM:
         eos = None
         if eos_token_id is not None:
             eos = [int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id]
-        token = int(ops.argmax(out.logits[:, -1, :].contiguous())[0])
+        if sample is None:
+            token = int(ops.argmax(out.logits[:, -1, :].contiguous())[0])
+        else:                                                # ``_generate``'s first draw: the counter is the prompt's length
+            sample = sample.to(self.device)
+            token = int(ops.argmax(out.logits[:, -1, :].contiguous(), sampling=sample, ctr_add=S)[0])
         new = [token]
         sess, plain, plain_steps = None, None, 0
 
@@ -790,13 +817,18 @@ class ValleyLlamaForCausalLM:
                 break
             if plain is None and cache.seq_len + k + 1 <= cache.ctx_max:
                 if sess is None:
-                    sess = SpecDecodeSession(self.model.llama, cache, k, max_ngram, eos_ids=eos, use_graph=use_graph)
+                    sess = SpecDecodeSession(self.model.llama, cache, k, max_ngram, eos_ids=eos, use_graph=use_graph,
+                                             sampling=sample is not None)
+                    if sample is not None:
+                        sess.sample.copy_(sample.expand(k + 1, 6))
                     known = torch.cat([input_ids[0], torch.tensor(new[:-1], dtype=input_ids.dtype, device=self.device)])
                     sess.begin(torch.tensor(new[-1:], device=self.device), prompt_ids=known)
                 emitted = sess.step()
             else:                                            # the cache's last positions: one token per step
                 if plain is None:
-                    plain = DecodeSession(self.model.llama, cache, use_graph=use_graph)
+                    plain = DecodeSession(self.model.llama, cache, use_graph=use_graph, sampling=sample is not None)
+                    if sample is not None:               # its counters go on from the cache's position: the seed's sequence
+                        plain.sample.copy_(sample)
                     plain.begin(torch.tensor([new[-1]], device=self.device))
                 emitted = [int(plain.step()[0])]
                 plain_steps += 1
@@ -1167,7 +1199,7 @@ class ValleyLlamaForCausalLM:
                                                             "length_penalty", "early_stopping", "repetition_penalty",
                                                             "no_repeat_ngram_size", "min_length", "min_new_tokens",
                                                             "output_logprobs", "top_logprobs", "prompt_lookup_num_tokens",
-                                                            "max_matching_ngram_size")}
+                                                            "max_matching_ngram_size", "seed")}
         self.last_generation = None
         if gk.get("output_logprobs"):                        # the log-probabilities of the answer: kept on ``last_generation``
             self.last_generation = self.generate(input_ids=input_ids, images=images, stopping_criteria=[stopping],
