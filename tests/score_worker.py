@@ -22,7 +22,7 @@ def main():
     seq = model.generate(torch.from_numpy(ids).cuda(), images=img, max_new_tokens=4)
     out = model.generate(torch.from_numpy(ids).cuda(), images=img, max_new_tokens=4, return_dict_in_generate=True)
     res = {"new_tokens": int(seq.shape[1] - ids.shape[1]), "same": bool(torch.equal(seq, out.sequences)),
-           "has_logprobs": hasattr(out, "token_logprobs"), "score_lib_loaded": lib_score._LIB is not None,
+           "has_logprobs": hasattr(out, "token_logprobs"), "score_lib_loaded": lib_score.loaded(),
            "score_lib_mapped": "libvalley_hip_score" in open("/proc/self/maps").read(), "ok": True}
     print(json.dumps(res))
 

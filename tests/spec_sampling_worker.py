@@ -41,11 +41,11 @@ def main():
     else:
         seq = model.generate(ids, images=img, max_new_tokens=4, **sampled)
         res["new_tokens"] = int(seq.shape[1] - ids.shape[1])
-        res["spec_lib_loaded"] = lib_spec._LIB is not None or "valley_amd.spec" in sys.modules
-        res["spec_sample_lib_loaded"] = lib_spec_sample._LIB is not None
+        res["spec_lib_loaded"] = lib_spec.loaded() or "valley_amd.spec" in sys.modules
+        res["spec_sample_lib_loaded"] = lib_spec_sample.loaded()
         model.generate(ids, images=img, max_new_tokens=12, prompt_lookup_num_tokens=3)
-        res["greedy_lookup_loads_spec"] = lib_spec._LIB is not None
-        res["greedy_lookup_loads_spec_sample"] = lib_spec_sample._LIB is not None
+        res["greedy_lookup_loads_spec"] = lib_spec.loaded()
+        res["greedy_lookup_loads_spec_sample"] = lib_spec_sample.loaded()
     res["ok"] = True
     print(json.dumps(res))
 

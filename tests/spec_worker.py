@@ -44,7 +44,7 @@ def main():
         model, ids, img = golden_inputs()
         seq = model.generate(ids, images=img, max_new_tokens=4)
         res["new_tokens"] = int(seq.shape[1] - ids.shape[1])
-        res["spec_lib_loaded"] = lib_spec._LIB is not None or "valley_amd.spec" in sys.modules
+        res["spec_lib_loaded"] = lib_spec.loaded() or "valley_amd.spec" in sys.modules
     res["ok"] = True
     print(json.dumps(res))
 

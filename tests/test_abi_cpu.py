@@ -38,14 +38,9 @@ def test_library_exports_every_declared_symbol():
 def test_exported_symbols_are_exactly_the_header(tmp_path):
     """`nm -D` of the two shipped libraries = the header's default section = the ctypes binding (the libraries carry only
     what a default path calls); the experimental library adds exactly the header's EXPERIMENTAL prototypes."""
-    import subprocess
+    from tests.test_companions_cpu import exported
     from valley_amd import build, lib
     build.build(verbose=False)
-
-    def exported(path):
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        return sorted(ln.split()[-1] for ln in out.splitlines() if re.search(r" T vly_[a-z0-9_]+$", ln))
-
     names, exp_names = header_symbols(), header_symbols(experimental=True)
     assert exported(build.LIB) == names == exported(build.LIB_F16)
     assert len(names) <= 52, len(names)          # (round 6: + vly_split3_f32, vly_norm_split3_f32)

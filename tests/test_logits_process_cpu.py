@@ -1,59 +1,19 @@
-"""Logits processors without a GPU: the companion library's exports, ABI version and host-side argument checks; the
+"""Logits processors without a GPU: the companion library's host-side argument checks (its exports and ABI version:
+tests/test_companions_cpu.py); the
 parameter table and its HF messages; and the reference loops of tests/test_logits_process_gpu.py (tests/logits_ref.py)
 pinned to ``LlamaForCausalLM.generate`` on a tiny CPU Llama, greedy and beam, over a grid of processor settings."""
-import os
-import re
-import subprocess
-
 import pytest
 import torch
 
 from tests import logits_ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EOS = 7
 V = 101
 
 
-def header_symbols():
-    txt = open(os.path.join(ROOT, "include", "valley_hip_logits.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(vly_[a-z0-9_]+)\s*\(", txt)))
-
-
-def exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return sorted(ln.split()[-1] for ln in out.splitlines() if re.search(r" T vly_[a-z0-9_]+$", ln))
-
-
-def test_logits_library_exports_exactly_its_header():
-    from valley_amd import build, lib_logits
-    build.build(verbose=False)
-    names = header_symbols()
-    assert exported(build.LIB_LOGITS) == names == sorted(lib_logits.EXPORTS)
-    assert {"vly_logits_process", "vly_logits_history_gather", "vly_logits_beam_candidates"} <= set(names)
-    assert lib_logits.load_logits().vly_logits_abi_version() == lib_logits.ABI_VERSION == 1
-    hdr = open(os.path.join(ROOT, "include", "valley_hip_logits.h")).read()
-    assert re.search(r"#define VLY_LOGITS_ABI_VERSION 1\b", hdr)
-
-
-def test_main_and_beam_libraries_export_what_they_did():
-    from tests.test_abi_cpu import header_symbols as main_symbols
-    from tests.test_beam_cpu import header_symbols as beam_symbols
-    from valley_amd import build, lib, lib_beam
-    build.build(verbose=False)
-    names = main_symbols()
-    assert len(names) == 52 and lib.ABI_VERSION == 8
-    for path in (build.LIB, build.LIB_F16):
-        got = exported(path)
-        assert got == names and not any("logits_" in n for n in got)
-    assert exported(build.LIB_BEAM) == beam_symbols() == sorted(lib_beam.EXPORTS)
-    assert lib_beam.load_beam().vly_beam_abi_version() == 1
-
-
 def test_logits_library_rejects_bad_arguments_without_a_gpu():
     from valley_amd import lib_logits
-    h = lib_logits.load_logits()
+    h = lib_logits.load()
     # logits_process(logits, ld, V, R, params, hist, hist_ld, len, per_row, len_add, tok, eos, n_eos, log_softmax, stream)
     assert h.vly_logits_process(None, 10, 10, 1, None, None, 8, None, 0, 0, None, None, 0, 0, None) == -22
     assert b"vly_logits_process" in h.vly_logits_last_error()
@@ -69,7 +29,7 @@ def test_logits_library_rejects_bad_arguments_without_a_gpu():
     assert h.vly_logits_beam_scratch_bytes(2, 4, 8) >= 2 * 4 * 8 * 8
     assert h.vly_logits_beam_scratch_bytes(0, 4, 8) == 0
     from valley_amd import lib_beam
-    assert h.vly_logits_beam_scratch_bytes(3, 4, 12) == lib_beam.load_beam().vly_beam_scratch_bytes(3, 4, 12)
+    assert h.vly_logits_beam_scratch_bytes(3, 4, 12) == lib_beam.load().vly_beam_scratch_bytes(3, 4, 12)
 
 
 def hf_message(fn):

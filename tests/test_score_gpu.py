@@ -92,7 +92,7 @@ def test_rows_equal_logits_process_bit_for_bit(V):
             assert bool((copy[:, V:] == 7.0).all())
         assert torch.equal(bits(xd), bits(orig))                                    # read only; the poisoned padding as it was
     # outputs the call was not asked for are not written: n_top = 0 with buffers given, no target, no lse, no copy
-    h = lib_score.load_score()
+    h = lib_score.load()
     sid = torch.full((SR.ROWS, 4), 12345, dtype=torch.int32, device=dev())
     slp = torch.full((SR.ROWS, 4), 5.5, device=dev())
     lse2 = torch.full((SR.ROWS,), 9.0, device=dev())

@@ -1,55 +1,13 @@
-"""CPU-side checks of prompt-lookup speculation under seeded sampling: libvalley_hip_spec_sample.so exports exactly its header
-(and the spec library keeps its five exports and its ABI version), ops.spec_counters checks its arguments before any launch,
-generate() admits do_sample=True with a seed and with a seed only, and completion() / the command lines pass the seed on."""
-import os
-import re
-import subprocess
-
+"""CPU-side checks of prompt-lookup speculation under seeded sampling: the library and ops.spec_counters check
+their arguments before any launch, generate() admits do_sample=True with a seed and with a seed only, and
+completion() / the command lines pass the seed on."""
 import pytest
 import torch
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "valley_hip_spec_sample.h")
-
-
-def header_symbols():
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(vly_spec_[a-z0-9_]+)\s*\(", txt)))
-
-
-def exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return sorted(ln.split()[-1] for ln in out.splitlines() if re.search(r" T vly_[a-z0-9_]+$", ln))
-
-
-def test_header_declares_the_counters_and_the_library_exports_them():
-    from valley_amd import build, lib_spec, lib_spec_sample, ops
-    build.build(verbose=False)
-    names = header_symbols()
-    assert names == ["vly_spec_counters", "vly_spec_sample_abi_version", "vly_spec_sample_last_error"]
-    assert exported(build.LIB_SPEC_SAMPLE) == names == sorted(lib_spec_sample.EXPORTS)
-    hdr = open(HEADER).read()
-    assert re.search(r"#define VLY_SPEC_SAMPLE_ABI_VERSION 1\b", hdr)
-    assert lib_spec_sample.load_spec_sample().vly_spec_sample_abi_version() == lib_spec_sample.ABI_VERSION == 1
-    assert int(re.search(r"#define VLY_SPEC_SAMPLE_MAX_DRAFT (\d+)\b", hdr).group(1)) == lib_spec_sample.MAX_DRAFT == \
-        ops.SPEC_MAX_DRAFT == lib_spec.MAX_DRAFT
-    assert re.search(r"int vly_spec_counters\(const int32_t \*pos_dev, int k, int ctx_max, int32_t \*ctr, void \*stream\);", hdr)
-    # the companion it joins is what it was: no new export there, the same ABI version
-    assert "vly_spec_counters" not in exported(build.LIB_SPEC) and len(exported(build.LIB_SPEC)) == 5
-    assert lib_spec.load_spec().vly_spec_abi_version() == 1
-
-
-def test_missing_library_fails_loudly(monkeypatch, tmp_path):
-    from valley_amd import lib, lib_spec_sample
-    monkeypatch.setattr(lib_spec_sample, "_LIB", None)
-    monkeypatch.setenv("VALLEY_HIP_SPEC_SAMPLE_LIB", str(tmp_path / "nope.so"))
-    with pytest.raises(lib.ValleyHipError):
-        lib_spec_sample.load_spec_sample()
 
 
 def test_bad_arguments_are_refused_by_the_library():
     from valley_amd import lib_spec_sample
-    h = lib_spec_sample.load_spec_sample()
+    h = lib_spec_sample.load()
     ok = 4096
     for args in ((None, 3, 64, ok), (ok, 3, 64, None), (ok, 0, 64, ok), (ok, 8, 64, ok), (ok, 3, 3, ok), (ok, 3, 0, ok),
                  (ok + 2, 3, 64, ok), (ok, 3, 64, ok + 1)):

@@ -23,7 +23,7 @@ def main():
         assert runtime.HALF == torch.float16
         w4_checks.run_all()
         res["storage"] = lib.load().vly_storage_dtype()
-        res["wq_lib_loaded"] = lib_wq._LIB is not None
+        res["wq_lib_loaded"] = lib_wq.loaded()
     else:
         assert not os.environ.get("VALLEY_WEIGHT_QUANT")
         from tests import golden_cfg as G
@@ -39,8 +39,8 @@ def main():
         res["new_tokens"] = int(seq.shape[1] - ids.shape[1])
         res["weight_quant"] = ll.weight_quant
         res["wq_keys"] = sorted(k for L in ll.layers for k in L if k.startswith("wq_"))
-        res["w4_lib_loaded"] = lib_w4._LIB is not None
-        res["wq_lib_loaded"] = lib_wq._LIB is not None
+        res["w4_lib_loaded"] = lib_w4.loaded()
+        res["wq_lib_loaded"] = lib_wq.loaded()
     res["ok"] = True
     print(json.dumps(res))
 

@@ -37,7 +37,7 @@ def main():
         res["new_tokens"] = int(seq.shape[1] - ids.shape[1])
         res["weight_quant"] = ll.weight_quant
         res["wq_keys"] = sorted(k for L in ll.layers for k in L if k.startswith("wq_"))
-        res["wq_lib_loaded"] = lib_wq._LIB is not None
+        res["wq_lib_loaded"] = lib_wq.loaded()
     res["ok"] = True
     print(json.dumps(res))
 

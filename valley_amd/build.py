@@ -5,6 +5,7 @@ from __future__ import annotations
 import os
 import subprocess
 import sys
+from typing import NamedTuple
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
@@ -16,38 +17,40 @@ LIB_F16 = os.path.join(LIBDIR, "libvalley_hip_f16.so")      # the same sources w
 LIB_EXP = os.path.join(LIBDIR, "libvalley_hip_exp.so")
 LIB_EXP_F16 = os.path.join(LIBDIR, "libvalley_hip_exp_f16.so")   # the same on fp16 storage (the experiments' bit-identity tests run on both types)
 EXP_UNITS = ["decode_step.hip", "attention.hip", "gemm_bf16.hip", "gemv_bf16.hip"]
-# the beam-search kernels (include/valley_hip_beam.h): a companion library of their own, independent of the storage type — one
-# build serves the bf16 and fp16 libraries and the fp32 engine; the shipped libraries' exports stay exactly valley_hip.h's
-LIB_BEAM = os.path.join(LIBDIR, "libvalley_hip_beam.so")
-BEAM_SOURCES = ["beam.hip"]
-# the logits processors (include/valley_hip_logits.h): another companion of the same kind, fp32 logits and int32 ids only
-LIB_LOGITS = os.path.join(LIBDIR, "libvalley_hip_logits.so")
-LOGITS_SOURCES = ["logits.hip"]
-# weight-only INT8 decode (include/valley_hip_wq.h): the quantizer and the int8 weight-streaming GEMVs; one build serves both
-# 16-bit storage types (every compute entry takes the dtype code), so the main libraries' exports stay exactly valley_hip.h's
-LIB_WQ = os.path.join(LIBDIR, "libvalley_hip_wq.so")
-WQ_SOURCES = ["wq.hip"]
-# weight-only INT4 decode (include/valley_hip_w4.h): the group quantizer (one fp32 scale per 128 weights) and the 4-bit
-# weight-streaming GEMVs; a companion of the same kind as the wq library (dtype code, loaded on first use)
-LIB_W4 = os.path.join(LIBDIR, "libvalley_hip_w4.so")
-W4_SOURCES = ["w4.hip"]
-# token log-probabilities and the forward-only loss (include/valley_hip_score.h): fp32 logits and int32 ids only, like the logits
-# processors, whose log-sum-exp routine (beam_rows.inc) it compiles; loaded on first use
-LIB_SCORE = os.path.join(LIBDIR, "libvalley_hip_score.so")
-SCORE_SOURCES = ["score.hip"]
-# prompt-lookup speculative decoding (include/valley_hip_spec.h): the split attention of the verify step's k + 1 queries, the draft
-# lookup and the acceptance; one build serves both 16-bit storage types (dtype code, as the wq library); loaded on first use
-LIB_SPEC = os.path.join(LIBDIR, "libvalley_hip_spec.so")
-SPEC_SOURCES = ["spec.hip"]
-# the draw counters of a verify step under seeded sampling (include/valley_hip_spec_sample.h): int32 only; a companion of its
-# own so that the spec library's exports and ABI version stay what they were; loaded by a sampled speculative generation only
-LIB_SPEC_SAMPLE = os.path.join(LIBDIR, "libvalley_hip_spec_sample.so")
-SPEC_SAMPLE_SOURCES = ["spec_sample.hip"]
-# the row top-K and merge that the beam and logits companions compile (beam candidates over log-softmax and over processed
-# scores), and the log-sum-exp routine the score companion shares with them
-COMPANION_SHARED = ["beam_rows.inc"]
-# the headers the other companions compile instead: qgemv.hpp is the GEMV skeleton the two weight-only formats share
-COMPANION_DEPS = {"wq": ["common.hpp", "qgemv.hpp"], "w4": ["common.hpp", "qgemv.hpp"], "spec": ["common.hpp"], "spec_sample": []}
+# The companion libraries: one feature each, with its own public header (include/valley_hip_<name>.h) and ABI version, loaded on
+# first use (valley_amd/companion.py), so that the shipped libraries' exports stay exactly valley_hip.h's.  None depends on how the
+# main libraries were compiled: one build serves the bf16 and fp16 libraries and the fp32 engine (fp32 logits and int32 ids only, or
+# the 16-bit storage type as an argument).  DESIGN.md "adding a companion library" is the recipe.
+LIB_BEAM = os.path.join(LIBDIR, "libvalley_hip_beam.so")                   # beam search: candidates, selection, KV reorder
+LIB_LOGITS = os.path.join(LIBDIR, "libvalley_hip_logits.so")               # the logits processors
+LIB_WQ = os.path.join(LIBDIR, "libvalley_hip_wq.so")                       # weight-only INT8 decode: row quantizer and GEMVs
+LIB_W4 = os.path.join(LIBDIR, "libvalley_hip_w4.so")                       # weight-only INT4 decode: group quantizer and GEMVs
+LIB_SCORE = os.path.join(LIBDIR, "libvalley_hip_score.so")                 # token log-probabilities and the forward-only loss
+LIB_SPEC = os.path.join(LIBDIR, "libvalley_hip_spec.so")                   # prompt-lookup speculation: attention, draft, acceptance
+LIB_SPEC_SAMPLE = os.path.join(LIBDIR, "libvalley_hip_spec_sample.so")     # the verify step's draw counters under seeded sampling
+# the C prologue every companion compiles (error text, launch check, the version / last-error entry points)
+COMPANION_SHARED = ["companion_capi.hpp"]
+
+
+class Companion(NamedTuple):
+    name: str          # libvalley_hip_<name>.so, objects under lib/<name>/, entry points vly_<name>_*, binding lib_<name>.py
+    lib: str
+    sources: tuple     # translation units under csrc/
+    header: str        # the public header under include/
+    deps: tuple        # what the sources include from csrc/ besides COMPANION_SHARED
+
+
+# beam_rows.inc: the row top-K and merge of the beam and logits companions and the log-sum-exp the score companion shares with them;
+# qgemv.hpp: the GEMV skeleton the two weight-only formats share
+COMPANIONS = (
+    Companion("beam", LIB_BEAM, ("beam.hip",), "valley_hip_beam.h", ("beam_rows.inc",)),
+    Companion("logits", LIB_LOGITS, ("logits.hip",), "valley_hip_logits.h", ("beam_rows.inc",)),
+    Companion("wq", LIB_WQ, ("wq.hip",), "valley_hip_wq.h", ("common.hpp", "qgemv.hpp")),
+    Companion("score", LIB_SCORE, ("score.hip",), "valley_hip_score.h", ("beam_rows.inc",)),
+    Companion("spec", LIB_SPEC, ("spec.hip",), "valley_hip_spec.h", ("common.hpp",)),
+    Companion("w4", LIB_W4, ("w4.hip",), "valley_hip_w4.h", ("common.hpp", "qgemv.hpp")),
+    Companion("spec_sample", LIB_SPEC_SAMPLE, ("spec_sample.hip",), "valley_hip_spec_sample.h", ()),
+)
 SOURCES = ["capi.hip", "gemm_bf16.hip", "gemm_p32.hip", "gemm_p16.hip", "gemm_streamk.hip", "norm_elementwise.hip", "attention.hip", "temporal_delta.hip", "preprocess.hip", "gemv_bf16.hip", "precise_f32.hip", "gemm_skinny.hip", "decode_step.hip", "sampling.hip"]
 
 
@@ -63,10 +66,8 @@ def hipcc() -> str:
 
 def needs_build() -> bool:
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h)
-                                                                 for h in ("valley_hip.h", "valley_hip_beam.h", "valley_hip_logits.h", "valley_hip_wq.h",
-                                                                           "valley_hip_score.h", "valley_hip_spec.h", "valley_hip_w4.h",
-                                                                           "valley_hip_spec_sample.h")]
-    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, LIB_BEAM, LIB_LOGITS, LIB_WQ, LIB_SCORE, LIB_SPEC, LIB_W4, LIB_SPEC_SAMPLE):
+                                                                 for h in ("valley_hip.h", *(c.header for c in COMPANIONS))]
+    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, *(c.lib for c in COMPANIONS)):
         if not os.path.exists(lib):
             return True
         t = os.path.getmtime(lib)
@@ -78,16 +79,8 @@ def needs_build() -> bool:
 def build(force: bool = False, verbose: bool = True) -> str:
     """The two shipped libraries (bf16 and fp16 storage) and the experimental one, every stale translation unit compiled in parallel."""
     os.makedirs(LIBDIR, exist_ok=True)
-    os.makedirs(os.path.join(LIBDIR, "f16"), exist_ok=True)
-    os.makedirs(os.path.join(LIBDIR, "exp"), exist_ok=True)
-    os.makedirs(os.path.join(LIBDIR, "exp_f16"), exist_ok=True)
-    os.makedirs(os.path.join(LIBDIR, "beam"), exist_ok=True)
-    os.makedirs(os.path.join(LIBDIR, "logits"), exist_ok=True)
-    os.makedirs(os.path.join(LIBDIR, "wq"), exist_ok=True)
-    os.makedirs(os.path.join(LIBDIR, "score"), exist_ok=True)
-    os.makedirs(os.path.join(LIBDIR, "spec"), exist_ok=True)
-    os.makedirs(os.path.join(LIBDIR, "w4"), exist_ok=True)
-    os.makedirs(os.path.join(LIBDIR, "spec_sample"), exist_ok=True)
+    for sub in ("f16", "exp", "exp_f16", *(c.name for c in COMPANIONS)):
+        os.makedirs(os.path.join(LIBDIR, sub), exist_ok=True)
     if not force and not needs_build():
         return LIB
     variants = [(LIB, LIBDIR, [], SOURCES), (LIB_F16, os.path.join(LIBDIR, "f16"), ["-DVLY_FP16=1"], SOURCES),
@@ -115,17 +108,13 @@ def build(force: bool = False, verbose: bool = True) -> str:
             jobs.append((s, cmd))
             if s in AUDITED:
                 audits.append((s, odir, " ".join(flags) or "(default flags)"))
-    companions = [(LIB_BEAM, "beam", BEAM_SOURCES, "valley_hip_beam.h"), (LIB_LOGITS, "logits", LOGITS_SOURCES, "valley_hip_logits.h"),
-                  (LIB_WQ, "wq", WQ_SOURCES, "valley_hip_wq.h"), (LIB_SCORE, "score", SCORE_SOURCES, "valley_hip_score.h"),
-                  (LIB_SPEC, "spec", SPEC_SOURCES, "valley_hip_spec.h"), (LIB_W4, "w4", W4_SOURCES, "valley_hip_w4.h"),
-                  (LIB_SPEC_SAMPLE, "spec_sample", SPEC_SAMPLE_SOURCES, "valley_hip_spec_sample.h")]
-    for _lib, sub, units, header in companions:
-        cdir = os.path.join(LIBDIR, sub)
-        for s in units:
+    for c in COMPANIONS:
+        cdir = os.path.join(LIBDIR, c.name)
+        for s in c.sources:
             o = os.path.join(cdir, s.replace(".hip", ".o"))
             t_dep = max([os.path.getmtime(os.path.join(CSRC, s)), os.path.getmtime(os.path.abspath(__file__)),
-                         os.path.getmtime(os.path.join(HERE, "..", "include", header))] +
-                        [os.path.getmtime(os.path.join(CSRC, f)) for f in COMPANION_DEPS.get(sub, COMPANION_SHARED)])
+                         os.path.getmtime(os.path.join(HERE, "..", "include", c.header))] +
+                        [os.path.getmtime(os.path.join(CSRC, f)) for f in (*COMPANION_SHARED, *c.deps)])
             if force or not os.path.exists(o) or os.path.getmtime(o) < t_dep:
                 jobs.append((s, [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-save-temps=obj", "-c",
                                  os.path.join(CSRC, s), "-o", o]))
@@ -169,9 +158,9 @@ def build(force: bool = False, verbose: bool = True) -> str:
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
-    for lib, sub, units, _header in companions:
-        cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + \
-            [os.path.join(LIBDIR, sub, s.replace(".hip", ".o")) for s in units]
+    for c in COMPANIONS:
+        cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", c.lib] + \
+            [os.path.join(LIBDIR, c.name, s.replace(".hip", ".o")) for s in c.sources]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)

@@ -5,31 +5,12 @@
 //
 // This unit is compiled into its own library and includes no storage-type header: nothing here depends on bf16 / fp16.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
+#include "companion_capi.hpp"
 #include "../../include/valley_hip_beam.h"
 
 namespace {
-
-thread_local char g_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-int check_launch(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("%s: launch failed: %s", what, hipGetErrorString(e));
-        return -(1000 + (int)e);
-    }
-    return 0;
-}
 
 #include "beam_rows.inc"
 
@@ -107,8 +88,7 @@ __global__ void __launch_bounds__(RO_THREADS) kv_reorder_kernel(const int64_t* _
 
 }  // namespace
 
-extern "C" int vly_beam_abi_version(void) { return VLY_BEAM_ABI_VERSION; }
-extern "C" const char* vly_beam_last_error(void) { return g_err; }
+VLY_COMPANION_CAPI(beam, VLY_BEAM_ABI_VERSION)
 
 extern "C" size_t vly_beam_scratch_bytes(int B, int nb, int K) { return beam_scratch_bytes(B, nb, K); }
 

@@ -9,31 +9,12 @@
 //
 // This unit is compiled into its own library and includes no storage-type header: nothing here depends on bf16 / fp16.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
+#include "companion_capi.hpp"
 #include "../../include/valley_hip_logits.h"
 
 namespace {
-
-thread_local char g_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-int check_launch(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("%s: launch failed: %s", what, hipGetErrorString(e));
-        return -(1000 + (int)e);
-    }
-    return 0;
-}
 
 #include "beam_rows.inc"
 
@@ -132,8 +113,7 @@ __global__ void __launch_bounds__(G_THREADS) history_gather_kernel(int32_t* __re
 
 }  // namespace
 
-extern "C" int vly_logits_abi_version(void) { return VLY_LOGITS_ABI_VERSION; }
-extern "C" const char* vly_logits_last_error(void) { return g_err; }
+VLY_COMPANION_CAPI(logits, VLY_LOGITS_ABI_VERSION)
 
 extern "C" int vly_logits_process(float* logits, int ld, int V, int R, const int32_t* params, int32_t* hist, int hist_ld,
                                   const int32_t* len_dev, int len_per_row, int len_add, const int32_t* tok, const int32_t* eos,

@@ -22,36 +22,17 @@
 // conversions are templates here; they are common.hpp's expressions (h_lo / h_hi / f2h / pack_h2) for the type named.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include <type_traits>
 
 #include "common.hpp"
+#include "companion_capi.hpp"
 
 namespace {
 
 // the epilogue and output codes of valley_hip_wq.h and valley_hip_w4.h (each format file asserts that its header agrees)
 enum { QG_EPI_NONE = 0, QG_EPI_SWIGLU = 2, QG_OUT_16 = 0, QG_OUT_F32 = 1 };
-
-thread_local char g_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-int check_launch(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("%s: launch failed: %s", what, hipGetErrorString(e));
-        return -(1000 + (int)e);
-    }
-    return 0;
-}
 
 typedef __attribute__((ext_vector_type(2))) _Float16 qg_f16x2;
 typedef __attribute__((ext_vector_type(2))) __bf16 qg_bf16x2;

@@ -10,31 +10,12 @@
 //
 // This unit is compiled into its own library and includes no storage-type header: nothing here depends on bf16 / fp16.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
+#include "companion_capi.hpp"
 #include "../../include/valley_hip_score.h"
 
 namespace {
-
-thread_local char g_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-int check_launch(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("%s: launch failed: %s", what, hipGetErrorString(e));
-        return -(1000 + (int)e);
-    }
-    return 0;
-}
 
 #include "beam_rows.inc"
 
@@ -179,8 +160,7 @@ __global__ void __launch_bounds__(LOSS_THREADS) score_loss_kernel(const float* _
 
 }  // namespace
 
-extern "C" int vly_score_abi_version(void) { return VLY_SCORE_ABI_VERSION; }
-extern "C" const char* vly_score_last_error(void) { return g_err; }
+VLY_COMPANION_CAPI(score, VLY_SCORE_ABI_VERSION)
 
 extern "C" int vly_score_rows(const float* logits, int ld, int V, int R, const int32_t* target, float* target_lp, float* lse, int n_top,
                               int32_t* top_id, float* top_lp, float* copy, int copy_ld, void* stream) {

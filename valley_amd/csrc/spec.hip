@@ -16,32 +16,13 @@
 // One build serves both 16-bit storage types (DT = 0: bf16, 1: IEEE fp16), as wq.hip does.
 #include <hip/hip_runtime.h>
 #include <limits.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "common.hpp"
+#include "companion_capi.hpp"
 #include "../../include/valley_hip_spec.h"
 
 namespace {
-
-thread_local char g_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-int check_launch(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("%s: launch failed: %s", what, hipGetErrorString(e));
-        return -(1000 + (int)e);
-    }
-    return 0;
-}
 
 typedef __attribute__((ext_vector_type(2))) _Float16 sp_f16x2;
 typedef __attribute__((ext_vector_type(2))) __bf16 sp_bf16x2;
@@ -383,8 +364,7 @@ int launch_attn(int S, dim3 grid, hipStream_t st, const uint16_t* qkv, const uin
 
 }  // namespace
 
-extern "C" int vly_spec_abi_version(void) { return VLY_SPEC_ABI_VERSION; }
-extern "C" const char* vly_spec_last_error(void) { return g_err; }
+VLY_COMPANION_CAPI(spec, VLY_SPEC_ABI_VERSION)
 
 extern "C" int vly_spec_attention(const void* qkv, const void* kcache, const void* vcache, const uint8_t* key_valid, int key_valid_stride,
                                   void* out, int B, int S, int heads, int past_len, const int32_t* past_len_dev, int ctx_max,

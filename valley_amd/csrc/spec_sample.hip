@@ -2,22 +2,12 @@
 // sampling.  Row j of the step draws the token of sequence index pos + j + 1 (vly_argmax: ctr[j] + ctr_add, ctr_add = 1), so the
 // table is pos + j with the position read — and clamped as the step's other kernels clamp it — on the device.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
+#include "companion_capi.hpp"
 #include "../../include/valley_hip_spec_sample.h"
 
 namespace {
-
-thread_local char g_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
 
 // one wave; lanes 0 .. k store one word each
 __global__ void __launch_bounds__(64) spec_counters_kernel(const int32_t* __restrict__ pos_dev, int k, int ctx_max,
@@ -30,8 +20,7 @@ __global__ void __launch_bounds__(64) spec_counters_kernel(const int32_t* __rest
 
 }  // namespace
 
-extern "C" int vly_spec_sample_abi_version(void) { return VLY_SPEC_SAMPLE_ABI_VERSION; }
-extern "C" const char* vly_spec_sample_last_error(void) { return g_err; }
+VLY_COMPANION_CAPI(spec_sample, VLY_SPEC_SAMPLE_ABI_VERSION)
 
 extern "C" int vly_spec_counters(const int32_t* pos_dev, int k, int ctx_max, int32_t* ctr, void* stream) {
     if (!pos_dev || !ctr || k < 1 || k > VLY_SPEC_SAMPLE_MAX_DRAFT || ctx_max < k + 1 || ((uintptr_t)pos_dev & 3) || ((uintptr_t)ctr & 3)) {
@@ -40,10 +29,5 @@ extern "C" int vly_spec_counters(const int32_t* pos_dev, int k, int ctx_max, int
         return -22;
     }
     hipLaunchKernelGGL(spec_counters_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, pos_dev, k, ctx_max, ctr);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("vly_spec_counters: launch failed: %s", hipGetErrorString(e));
-        return -(1000 + (int)e);
-    }
-    return 0;
+    return check_launch("vly_spec_counters");
 }

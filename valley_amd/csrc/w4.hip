@@ -229,9 +229,7 @@ __global__ void __launch_bounds__(256) w4_quantize_kernel(const uint16_t* __rest
 
 }  // namespace
 
-extern "C" int vly_w4_abi_version(void) { return VLY_W4_ABI_VERSION; }
-
-extern "C" const char* vly_w4_last_error(void) { return g_err; }
+VLY_COMPANION_CAPI(w4, VLY_W4_ABI_VERSION)
 
 extern "C" int vly_w4_quantize_rows(const void* w16, int ldw, int N, int K, int dtype, uint8_t* q_out, float* scale_out, void* stream) {
     if ((dtype != 0 && dtype != 1) || N <= 0 || K <= 0 || K % VLY_W4_GROUP || ldw % 8 || ldw < K || !w16 || !q_out || !scale_out ||

@@ -184,9 +184,7 @@ __global__ void __launch_bounds__(256) wq_quantize_kernel(const uint16_t* __rest
 
 }  // namespace
 
-extern "C" int vly_wq_abi_version(void) { return VLY_WQ_ABI_VERSION; }
-
-extern "C" const char* vly_wq_last_error(void) { return g_err; }
+VLY_COMPANION_CAPI(wq, VLY_WQ_ABI_VERSION)
 
 extern "C" int vly_wq_quantize_rows(const void* w16, int ldw, int N, int K, int dtype, int8_t* q_out, float* scale_out, void* stream) {
     if ((dtype != 0 && dtype != 1) || N <= 0 || K <= 0 || K % 16 || ldw % 8 || ldw < K || !w16 || !q_out || !scale_out ||

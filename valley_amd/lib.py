@@ -91,6 +91,17 @@ class ValleyHipError(RuntimeError):
     pass
 
 
+def bind(lib, path: str, sigs: dict) -> None:
+    """Type every function of sigs on the ctypes handle lib; a library that lacks one is refused by name."""
+    for name, (res, args) in sigs.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise ValleyHipError(f"{path} does not export {name}") from e
+        fn.restype = res
+        fn.argtypes = args
+
+
 def lib_path() -> str:
     """libvalley_hip.so (bf16 storage) or libvalley_hip_f16.so (VALLEY_PRECISION=fp16); VALLEY_HIP_LIB overrides."""
     from . import runtime
@@ -123,21 +134,12 @@ def _load_locked():
             f"{path} not found: build it with `python -m valley_amd.build` (hipcc --offload-arch=gfx950). "
             "valley_amd has no non-HIP compute path.")
     lib = ctypes.CDLL(path)
-    for name, (res, args) in _SIGS.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise ValleyHipError(f"{path} does not export {name}") from e
-        fn.restype = res
-        fn.argtypes = args
+    bind(lib, path, _SIGS)
     lib._vly_experimental = False
     try:
-        for name, (res, args) in _SIGS_EXPERIMENTAL.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
+        bind(lib, path, _SIGS_EXPERIMENTAL)
         lib._vly_experimental = True
-    except AttributeError:
+    except ValleyHipError:                                  # (the shipped libraries: bound when present)
         pass
     if lib.vly_abi_version() != ABI_VERSION:
         raise ValleyHipError(f"ABI mismatch: library {lib.vly_abi_version()} vs binding {ABI_VERSION}")

@@ -6,13 +6,10 @@ the dtype code).  Loaded on first use only: a run that never speculates never ma
 speculative decoding has no non-HIP path."""
 from __future__ import annotations
 
-import ctypes
-import os
-import threading
 from ctypes import c_char_p, c_int, c_void_p
 
 from . import build as _build
-from .lib import ValleyHipError
+from .companion import Companion
 
 _P = c_void_p
 SIGS = {
@@ -30,41 +27,5 @@ MAX_NGRAM = 8            # VLY_SPEC_MAX_NGRAM
 SPLITS = 4               # VLY_SPEC_SPLITS
 PARTIAL = 132            # VLY_SPEC_PARTIAL
 
-_LIB = None
-_LOCK = threading.Lock()
-
-
-def lib_path() -> str:
-    return os.environ.get("VALLEY_HIP_SPEC_LIB", _build.LIB_SPEC)
-
-
-def load_spec():
-    """Load (once) and type libvalley_hip_spec.so.  Raises if it is absent, incomplete or of another ABI version."""
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    with _LOCK:
-        if _LIB is not None:
-            return _LIB
-        path = lib_path()
-        if not os.path.exists(path):
-            raise ValleyHipError(f"{path} not found: build it with `python -m valley_amd.build` (hipcc --offload-arch=gfx950). "
-                                 "Speculative decoding has no non-HIP path.")
-        lib = ctypes.CDLL(path)
-        for name, (res, args) in SIGS.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise ValleyHipError(f"{path} does not export {name}") from e
-            fn.restype = res
-            fn.argtypes = args
-        if lib.vly_spec_abi_version() != ABI_VERSION:
-            raise ValleyHipError(f"spec ABI mismatch: library {lib.vly_spec_abi_version()} vs binding {ABI_VERSION}")
-        _LIB = lib
-        return lib
-
-
-def check(rc: int, what: str):
-    if rc != 0:
-        msg = load_spec().vly_spec_last_error().decode(errors="replace")
-        raise ValleyHipError(f"{what} failed (rc={rc}): {msg}")
+COMPANION = Companion("spec", SIGS, ABI_VERSION, _build.LIB_SPEC, "Speculative decoding has no non-HIP path.")
+load, loaded, check, lib_path, reset = COMPANION.load, COMPANION.loaded, COMPANION.check, COMPANION.lib_path, COMPANION.reset

@@ -1260,7 +1260,7 @@ def beam_k(nb: int, n_eos: int) -> int:
 def beam_scratch(B: int, nb: int, K: int, device) -> torch.Tensor:
     """The zeroed device scratch of ``beam_candidates`` (its ticket counters are back at zero after every launch)."""
     from . import lib_beam
-    n = int(lib_beam.load_beam().vly_beam_scratch_bytes(B, nb, K))
+    n = int(lib_beam.load().vly_beam_scratch_bytes(B, nb, K))
     if n <= 0:
         raise ValueError(f"beam_scratch: bad shape B={B} nb={nb} K={K}")
     return torch.zeros(((n + 255) // 256 * 256,), dtype=torch.uint8, device=device)
@@ -1283,7 +1283,7 @@ def beam_candidates(logits: torch.Tensor, running: torch.Tensor, B: int, nb: int
     if eos is not None:
         _chk(eos, torch.int32, "eos")
         n_eos = eos.numel()
-    need = int(lib_beam.load_beam().vly_beam_scratch_bytes(B, nb, K))
+    need = int(lib_beam.load().vly_beam_scratch_bytes(B, nb, K))
     if scratch.numel() < need:
         raise ValueError(f"beam_candidates: scratch holds {scratch.numel()} bytes, {need} needed")
     if out is None:
@@ -1294,7 +1294,7 @@ def beam_candidates(logits: torch.Tensor, running: torch.Tensor, B: int, nb: int
         _chk(t, dt, n)
         if t.numel() != B * K:
             raise ValueError(f"beam_candidates: {n} must hold {B * K} values")
-    rc = lib_beam.load_beam().vly_beam_candidates(logits.data_ptr(), logits.stride(0), V, B, nb, running.data_ptr(), K,
+    rc = lib_beam.load().vly_beam_candidates(logits.data_ptr(), logits.stride(0), V, B, nb, running.data_ptr(), K,
                                                   _ptr(eos) if n_eos else None, n_eos, scratch.data_ptr(),
                                                   *[t.data_ptr() for t in out], _stream())
     lib_beam.check(rc, "vly_beam_candidates")
@@ -1323,7 +1323,7 @@ def beam_select(score: torch.Tensor, token: torch.Tensor, beam: torch.Tensor, hi
         _chk(t, dt, name)
         if t.numel() != B * nb:
             raise ValueError(f"beam_select: {name} must hold {B * nb} values")
-    rc = lib_beam.load_beam().vly_beam_select(score.data_ptr(), token.data_ptr(), beam.data_ptr(), hit.data_ptr(), B, nb, K,
+    rc = lib_beam.load().vly_beam_select(score.data_ptr(), token.data_ptr(), beam.data_ptr(), hit.data_ptr(), B, nb, K,
                                               tok.data_ptr(), parent.data_ptr(), running.data_ptr(), _stream())
     lib_beam.check(rc, "vly_beam_select")
     return tok, parent, running
@@ -1364,7 +1364,7 @@ def kv_beam_reorder(table: torch.Tensor, kcache0: torch.Tensor, parent: torch.Te
     if pos_dev is not None:
         _chk(pos_dev, torch.int32, "pos_dev")
         pptr = pos_dev.data_ptr()
-    rc = lib_beam.load_beam().vly_kv_beam_reorder(table.data_ptr(), table.shape[0], R, heads, ctx_max, kcache0.element_size(),
+    rc = lib_beam.load().vly_kv_beam_reorder(table.data_ptr(), table.shape[0], R, heads, ctx_max, kcache0.element_size(),
                                                   parent.data_ptr(), int(lo), pptr, int(hi_add), _stream())
     lib_beam.check(rc, "vly_kv_beam_reorder")
 
@@ -1458,7 +1458,7 @@ def logits_process(logits: torch.Tensor, params: torch.Tensor, hist: torch.Tenso
     if eos is not None:
         _chk(eos, torch.int32, "eos")
         n_eos = eos.numel()
-    rc = lib_logits.load_logits().vly_logits_process(logits.data_ptr(), logits.stride(0), V, R, params.data_ptr(),
+    rc = lib_logits.load().vly_logits_process(logits.data_ptr(), logits.stride(0), V, R, params.data_ptr(),
                                                      hist.data_ptr(), hist.shape[1], lptr, per_row, int(len_add), _ptr(tok),
                                                      _ptr(eos) if n_eos else None, n_eos, int(bool(log_softmax)), _stream())
     lib_logits.check(rc, "vly_logits_process")
@@ -1479,7 +1479,7 @@ def logits_history_gather(hist: torch.Tensor, parent: torch.Tensor, lo: int, hi_
     if len_dev is not None:
         _chk(len_dev, torch.int32, "len_dev")
         lptr = len_dev.data_ptr()
-    rc = lib_logits.load_logits().vly_logits_history_gather(hist.data_ptr(), hist.shape[0], hist.shape[1], parent.data_ptr(),
+    rc = lib_logits.load().vly_logits_history_gather(hist.data_ptr(), hist.shape[0], hist.shape[1], parent.data_ptr(),
                                                             int(lo), lptr, int(hi_add), _stream())
     lib_logits.check(rc, "vly_logits_history_gather")
 
@@ -1500,7 +1500,7 @@ def logits_beam_candidates(scores: torch.Tensor, running: torch.Tensor, B: int, 
     if eos is not None:
         _chk(eos, torch.int32, "eos")
         n_eos = eos.numel()
-    h = lib_logits.load_logits()
+    h = lib_logits.load()
     need = int(h.vly_logits_beam_scratch_bytes(B, nb, K))
     if scratch.numel() < need:
         raise ValueError(f"logits_beam_candidates: scratch holds {scratch.numel()} bytes, {need} needed")
@@ -1573,7 +1573,7 @@ def token_logprobs(logits: torch.Tensor, targets: Optional[torch.Tensor] = None,
         _chk(tl, torch.float32, "top log-probabilities")
     if copy is not None:
         _chk(copy, torch.float32, "copy", contiguous=False)
-    rc = lib_score.load_score().vly_score_rows(logits.data_ptr(), logits.stride(0), V, R, _ptr(targets), _ptr(tlp), lse.data_ptr(),
+    rc = lib_score.load().vly_score_rows(logits.data_ptr(), logits.stride(0), V, R, _ptr(targets), _ptr(tlp), lse.data_ptr(),
                                                top, _ptr(tid), _ptr(tl), _ptr(copy), copy.stride(0) if copy is not None else 0,
                                                _stream())
     lib_score.check(rc, "vly_score_rows")
@@ -1619,7 +1619,7 @@ def score_record(raw: torch.Tensor, lse: torch.Tensor, tok: torch.Tensor, lp_tab
                                ("top ids", "top log-probabilities", "top id table", "top log-probability table")):
             _chk(t, dt, name)
         ptrs = [t.data_ptr() for t in list(top) + list(top_tables)]
-    rc = lib_score.load_score().vly_score_record(raw.data_ptr(), raw.stride(0), V, R, lse.data_ptr(), tok.data_ptr(), lptr, per_row,
+    rc = lib_score.load().vly_score_record(raw.data_ptr(), raw.stride(0), V, R, lse.data_ptr(), tok.data_ptr(), lptr, per_row,
                                                  int(len_add), lp_table.data_ptr(), L, n, *ptrs, _stream())
     lib_score.check(rc, "vly_score_record")
 
@@ -1643,7 +1643,7 @@ def nll_mean(target_lp: torch.Tensor, targets: torch.Tensor, V: int):
     _chk(targets, torch.int32, "targets")
     loss = torch.empty((), dtype=torch.float32, device=target_lp.device)
     count = torch.empty((), dtype=torch.int32, device=target_lp.device)
-    rc = lib_score.load_score().vly_score_loss(target_lp.data_ptr(), targets.data_ptr(), target_lp.numel(), int(V), loss.data_ptr(),
+    rc = lib_score.load().vly_score_loss(target_lp.data_ptr(), targets.data_ptr(), target_lp.numel(), int(V), loss.data_ptr(),
                                                count.data_ptr(), _stream())
     lib_score.check(rc, "vly_score_loss")
     return loss, count
@@ -1657,7 +1657,7 @@ W4_GROUP = 128           # VLY_W4_GROUP: consecutive k of a row that share one s
 
 class _QuantFormat(NamedTuple):
     """What one weight-only format brings to the shared implementation below."""
-    prefix: str                 # binding module lib_<prefix> with load_<prefix>(); entries vly_<prefix>_*
+    prefix: str                 # binding module lib_<prefix>; entries vly_<prefix>_*
     q_dtype: torch.dtype        # the packed weight's dtype
     k_mult: int                 # vly_<prefix>_gemv_rmsnorm takes K % k_mult == 0
     dtype_error: type           # what a tensor of the wrong dtype raises
@@ -1668,7 +1668,7 @@ class _QuantFormat(NamedTuple):
         """vly_<prefix>_<name>(*args) from the format's library, loaded on first use; a non-zero return raises."""
         mod = importlib.import_module(f"{__package__}.lib_{self.prefix}")
         full = f"vly_{self.prefix}_{name}"
-        mod.check(getattr(getattr(mod, f"load_{self.prefix}")(), full)(*args), full)
+        mod.check(getattr(mod.load(), full)(*args), full)
 
     def chk(self, t, dtype, name, contiguous=True):
         """_chk with the format's error for a wrong dtype."""
@@ -1863,7 +1863,7 @@ def spec_attention(qkv: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor
     if out is None:
         out = torch.empty((B * S, heads * 128), dtype=runtime.HALF, device=qkv.device)
     _chk(out, runtime.HALF, "out")
-    rc = lib_spec.load_spec().vly_spec_attention(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), _ptr(key_valid), kv_stride,
+    rc = lib_spec.load().vly_spec_attention(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), _ptr(key_valid), kv_stride,
                                                  out.data_ptr(), B, int(S), heads, int(past_len), _ptr(past_dev), ctx_max,
                                                  partials.data_ptr(), arrivals.data_ptr(), _wq_dtype(), _stream())
     lib_spec.check(rc, "vly_spec_attention")
@@ -1899,7 +1899,7 @@ def spec_draft(hist: torch.Tensor, length: Optional[torch.Tensor], len_add: int,
     for t, name in ((hist, "hist"), (draft, "draft"), (draft_len, "draft_len"), (tok, "tok")) + \
             (((length, "length"),) if length is not None else ()) + (((eos, "eos"),) if eos is not None else ()):
         _chk(t, torch.int32, name)
-    rc = lib_spec.load_spec().vly_spec_draft(hist.data_ptr(), hist.numel(), _ptr(length), int(len_add), k, int(max_ngram), _ptr(eos),
+    rc = lib_spec.load().vly_spec_draft(hist.data_ptr(), hist.numel(), _ptr(length), int(len_add), k, int(max_ngram), _ptr(eos),
                                              0 if eos is None else eos.numel(), int(vocab), int(bool(lookup)), draft.data_ptr(),
                                              draft_len.data_ptr(), tok.data_ptr(), _stream())
     lib_spec.check(rc, "vly_spec_draft")
@@ -1919,7 +1919,7 @@ def spec_accept(am: torch.Tensor, draft: torch.Tensor, draft_len: torch.Tensor, 
     for t, name in ((am, "am"), (draft, "draft"), (draft_len, "draft_len"), (hist, "hist"), (pos, "pos"), (emit, "emit"),
                     (tok, "tok"), (stats, "stats")):
         _chk(t, torch.int32, name)
-    rc = lib_spec.load_spec().vly_spec_accept(am.data_ptr(), draft.data_ptr(), draft_len.data_ptr(), k, hist.data_ptr(), hist.numel(),
+    rc = lib_spec.load().vly_spec_accept(am.data_ptr(), draft.data_ptr(), draft_len.data_ptr(), k, hist.data_ptr(), hist.numel(),
                                               pos.data_ptr(), emit.data_ptr(), tok.data_ptr(), stats.data_ptr(), _stream())
     lib_spec.check(rc, "vly_spec_accept")
 
@@ -1940,6 +1940,6 @@ def spec_counters(pos: torch.Tensor, k: int, ctx_max: int, out: torch.Tensor) ->
     from . import lib_spec_sample
     _chk(pos, torch.int32, "pos")
     _chk(out, torch.int32, "out")
-    rc = lib_spec_sample.load_spec_sample().vly_spec_counters(pos.data_ptr(), k, int(ctx_max), out.data_ptr(), _stream())
+    rc = lib_spec_sample.load().vly_spec_counters(pos.data_ptr(), k, int(ctx_max), out.data_ptr(), _stream())
     lib_spec_sample.check(rc, "vly_spec_counters")
     return out
