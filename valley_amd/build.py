@@ -28,6 +28,7 @@ LIB_W4 = os.path.join(LIBDIR, "libvalley_hip_w4.so")                       # wei
 LIB_SCORE = os.path.join(LIBDIR, "libvalley_hip_score.so")                 # token log-probabilities and the forward-only loss
 LIB_SPEC = os.path.join(LIBDIR, "libvalley_hip_spec.so")                   # prompt-lookup speculation: attention, draft, acceptance
 LIB_SPEC_SAMPLE = os.path.join(LIBDIR, "libvalley_hip_spec_sample.so")     # the verify step's draw counters under seeded sampling
+LIB_SPEC_ROWS = os.path.join(LIBDIR, "libvalley_hip_spec_rows.so")         # the verify step of several sequences, one position each
 # the C prologue every companion compiles (error text, launch check, the version / last-error entry points)
 COMPANION_SHARED = ["companion_capi.hpp"]
 
@@ -41,15 +42,20 @@ class Companion(NamedTuple):
 
 
 # beam_rows.inc: the row top-K and merge of the beam and logits companions and the log-sum-exp the score companion shares with them;
-# qgemv.hpp: the GEMV skeleton the two weight-only formats share
+# qgemv.hpp: the GEMV skeleton the two weight-only formats share; spec_attn.inc: the split attention of a verify step, which the
+# single-sequence companion and the per-sequence one (COMPANIONS_ROWS) instantiate with their own position source
 COMPANIONS = (
     Companion("beam", LIB_BEAM, ("beam.hip",), "valley_hip_beam.h", ("beam_rows.inc",)),
     Companion("logits", LIB_LOGITS, ("logits.hip",), "valley_hip_logits.h", ("beam_rows.inc",)),
     Companion("wq", LIB_WQ, ("wq.hip",), "valley_hip_wq.h", ("common.hpp", "qgemv.hpp")),
     Companion("score", LIB_SCORE, ("score.hip",), "valley_hip_score.h", ("beam_rows.inc",)),
-    Companion("spec", LIB_SPEC, ("spec.hip",), "valley_hip_spec.h", ("common.hpp",)),
+    Companion("spec", LIB_SPEC, ("spec.hip",), "valley_hip_spec.h", ("common.hpp", "spec_attn.inc")),
     Companion("w4", LIB_W4, ("w4.hip",), "valley_hip_w4.h", ("common.hpp", "qgemv.hpp")),
     Companion("spec_sample", LIB_SPEC_SAMPLE, ("spec_sample.hip",), "valley_hip_spec_sample.h", ()),
+)
+# batched speculation: a table of its own, walked by the same code (the seven above are what the other libraries' tests count)
+COMPANIONS_ROWS = (
+    Companion("spec_rows", LIB_SPEC_ROWS, ("spec_rows.hip",), "valley_hip_spec_rows.h", ("common.hpp", "spec_attn.inc")),
 )
 SOURCES = ["capi.hip", "gemm_bf16.hip", "gemm_p32.hip", "gemm_p16.hip", "gemm_streamk.hip", "norm_elementwise.hip", "attention.hip", "temporal_delta.hip", "preprocess.hip", "gemv_bf16.hip", "precise_f32.hip", "gemm_skinny.hip", "decode_step.hip", "sampling.hip"]
 
@@ -66,8 +72,8 @@ def hipcc() -> str:
 
 def needs_build() -> bool:
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h)
-                                                                 for h in ("valley_hip.h", *(c.header for c in COMPANIONS))]
-    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, *(c.lib for c in COMPANIONS)):
+                                                                 for h in ("valley_hip.h", *(c.header for c in (*COMPANIONS, *COMPANIONS_ROWS)))]
+    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, *(c.lib for c in (*COMPANIONS, *COMPANIONS_ROWS))):
         if not os.path.exists(lib):
             return True
         t = os.path.getmtime(lib)
@@ -79,7 +85,7 @@ def needs_build() -> bool:
 def build(force: bool = False, verbose: bool = True) -> str:
     """The two shipped libraries (bf16 and fp16 storage) and the experimental one, every stale translation unit compiled in parallel."""
     os.makedirs(LIBDIR, exist_ok=True)
-    for sub in ("f16", "exp", "exp_f16", *(c.name for c in COMPANIONS)):
+    for sub in ("f16", "exp", "exp_f16", *(c.name for c in (*COMPANIONS, *COMPANIONS_ROWS))):
         os.makedirs(os.path.join(LIBDIR, sub), exist_ok=True)
     if not force and not needs_build():
         return LIB
@@ -108,7 +114,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
             jobs.append((s, cmd))
             if s in AUDITED:
                 audits.append((s, odir, " ".join(flags) or "(default flags)"))
-    for c in COMPANIONS:
+    for c in (*COMPANIONS, *COMPANIONS_ROWS):
         cdir = os.path.join(LIBDIR, c.name)
         for s in c.sources:
             o = os.path.join(cdir, s.replace(".hip", ".o"))
@@ -158,7 +164,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
-    for c in COMPANIONS:
+    for c in (*COMPANIONS, *COMPANIONS_ROWS):
         cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", c.lib] + \
             [os.path.join(LIBDIR, c.name, s.replace(".hip", ".o")) for s in c.sources]
         if verbose:

@@ -1943,3 +1943,171 @@ def spec_counters(pos: torch.Tensor, k: int, ctx_max: int, out: torch.Tensor) ->
     rc = lib_spec_sample.load().vly_spec_counters(pos.data_ptr(), k, int(ctx_max), out.data_ptr(), _stream())
     lib_spec_sample.check(rc, "vly_spec_counters")
     return out
+
+
+# ---- batched prompt-lookup speculation (libvalley_hip_spec_rows.so, include/valley_hip_spec_rows.h) -------------------------
+# B sequences x S = k + 1 rows in one verify step, one device-side position per sequence (pos int32 [B]).  A row whose position
+# lies behind its sequence's cache is dead: it stores nothing.
+def _rows_pos(name: str, pos, B: int) -> None:
+    if not isinstance(pos, torch.Tensor) or pos.dtype != torch.int32 or pos.dim() != 1 or pos.numel() != B:
+        raise ValueError(f"{name}: pos must be int32 [{B}] (one position per sequence), got {getattr(pos, 'dtype', type(pos))} "
+                         f"{tuple(getattr(pos, 'shape', ()))}")
+
+
+def _rows_live(name: str, live, B: int) -> None:
+    if live is not None and (not isinstance(live, torch.Tensor) or live.dtype != torch.uint8 or live.dim() != 1 or live.numel() != B):
+        raise ValueError(f"{name}: live must be uint8 [{B}] or None, got {getattr(live, 'dtype', type(live))} "
+                         f"{tuple(getattr(live, 'shape', ()))}")
+
+
+def _rows_geometry(name: str, B: int, S: int, heads: int, qkv: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor) -> int:
+    if not 1 <= int(S) <= SPEC_MAX_QUERIES:
+        raise ValueError(f"{name}: S must be in [1, {SPEC_MAX_QUERIES}], got {S}")
+    if B < 1 or heads < 1:
+        raise ValueError(f"{name}: B >= 1 and heads >= 1 expected, got {B}, {heads}")
+    if kcache.dim() != 4 or tuple(kcache.shape[:2]) != (B, heads) or kcache.shape[3] != 128 or vcache.shape != kcache.shape:
+        raise ValueError(f"{name}: kcache / vcache [{B}, {heads}, ctx_max, 128] expected, got {tuple(kcache.shape)} / "
+                         f"{tuple(vcache.shape)}")
+    if tuple(qkv.shape) != (B * S, 3 * heads * 128):
+        raise ValueError(f"{name}: qkv [{B * S}, {3 * heads * 128}] expected, got {tuple(qkv.shape)}")
+    return kcache.shape[2]
+
+
+def spec_rows_scratch(B: int, S: int, heads: int, device):
+    """``(partials, arrivals)`` of ``spec_rows_attention`` for B sequences of S queries (``spec_scratch``'s layout)."""
+    return spec_scratch(B, S, heads, device)
+
+
+def spec_rows_rope_kv(qkv: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, B: int, S: int,
+                      heads: int, pos: torch.Tensor) -> None:
+    """vly_spec_rows_rope_kv: ``rope_kv`` of B sequences of S rows, sequence b at position pos[b] (clamped to [0, ctx_max - 1]):
+    q of qkv [B * S, 3 * heads * 128] rotated in place, rotated k and v to cache rows pos[b] + j.  A live row's bits are
+    ``rope_kv(B=1, S, past=pos[b])``'s; a row behind the cache's end is dead (nothing written, q left as it is)."""
+    ctx_max = _rows_geometry("spec_rows_rope_kv", B, S, heads, qkv, kcache, vcache)
+    _rows_pos("spec_rows_rope_kv", pos, B)
+    for t, name in ((cos, "cos"), (sin, "sin")):
+        if t.dim() != 2 or t.shape[0] < ctx_max or t.shape[1] != 64 or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"spec_rows_rope_kv: {name} fp32 [>= {ctx_max}, 64] expected, got {t.dtype} {tuple(t.shape)}")
+    from . import lib_spec_rows
+    _chk(qkv, runtime.HALF, "qkv")
+    _chk(kcache, runtime.HALF, "kcache")
+    _chk(vcache, runtime.HALF, "vcache")
+    _chk(cos, torch.float32, "cos")
+    _chk(sin, torch.float32, "sin")
+    _chk(pos, torch.int32, "pos")
+    rc = lib_spec_rows.load().vly_spec_rows_rope_kv(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), cos.data_ptr(), sin.data_ptr(), B,
+                                                    int(S), heads, pos.data_ptr(), ctx_max, _wq_dtype(), _stream())
+    lib_spec_rows.check(rc, "vly_spec_rows_rope_kv")
+
+
+def spec_rows_attention(qkv: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, key_valid: Optional[torch.Tensor], B: int, S: int,
+                        heads: int, pos: torch.Tensor, scratch, out=None) -> torch.Tensor:
+    """vly_spec_rows_attention: ``spec_attention`` with one position per sequence (pos int32 [B]).  The row of the query at
+    absolute position P is bit for bit the row ``spec_attention`` writes for that position: it does not depend on S, B, the
+    query's index or the other sequences' positions."""
+    ctx_max = _rows_geometry("spec_rows_attention", B, S, heads, qkv, kcache, vcache)
+    _rows_pos("spec_rows_attention", pos, B)
+    partials, arrivals = scratch
+    if partials.numel() < B * heads * S * SPEC_SPLITS * SPEC_PARTIAL or arrivals.numel() < B * heads:
+        raise ValueError("spec_rows_attention: scratch too small for this launch (ops.spec_rows_scratch(B, S, heads, device))")
+    kv_stride = 0
+    if key_valid is not None:
+        if key_valid.dim() != 2 or key_valid.shape[0] != B or key_valid.shape[1] < ctx_max or key_valid.stride(1) != 1:
+            raise ValueError(f"spec_rows_attention: key_valid [{B}, >= {ctx_max}] (the cache's ctx_max columns) expected, got "
+                             f"{tuple(key_valid.shape)}")
+        kv_stride = key_valid.stride(0)
+    if out is not None and tuple(out.shape) != (B * S, heads * 128):
+        raise ValueError(f"spec_rows_attention: out [{B * S}, {heads * 128}] expected, got {tuple(out.shape)}")
+    from . import lib_spec_rows
+    _chk(qkv, runtime.HALF, "qkv")
+    _chk(kcache, runtime.HALF, "kcache")
+    _chk(vcache, runtime.HALF, "vcache")
+    _chk(partials, torch.float32, "partials")
+    _chk(arrivals, torch.int32, "arrivals")
+    _chk(pos, torch.int32, "pos")
+    if key_valid is not None:
+        _chk(key_valid, torch.uint8, "key_valid", contiguous=False)
+    if out is None:
+        out = torch.empty((B * S, heads * 128), dtype=runtime.HALF, device=qkv.device)
+    _chk(out, runtime.HALF, "out")
+    rc = lib_spec_rows.load().vly_spec_rows_attention(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), _ptr(key_valid), kv_stride,
+                                                      out.data_ptr(), B, int(S), heads, pos.data_ptr(), ctx_max, partials.data_ptr(),
+                                                      arrivals.data_ptr(), _wq_dtype(), _stream())
+    lib_spec_rows.check(rc, "vly_spec_rows_attention")
+    return out
+
+
+def _rows_tables(name: str, B: int, k: int, hist, draft, draft_len, tok) -> None:
+    if hist.dim() != 2 or hist.shape[0] != B or hist.shape[1] < 1:
+        raise ValueError(f"{name}: hist [{B}, ctx_max] (one row per sequence) expected, got {tuple(hist.shape)}")
+    if tuple(draft.shape) != (B, k) or draft_len.numel() != B or tok.numel() != B * (k + 1):
+        raise ValueError(f"{name}: draft [{B}, {k}], draft_len [{B}] and tok [{B * (k + 1)}] expected, got {tuple(draft.shape)} / "
+                         f"{tuple(draft_len.shape)} / {tuple(tok.shape)}")
+
+
+def spec_rows_draft(hist: torch.Tensor, pos: torch.Tensor, len_add: int, k: int, max_ngram: int, draft: torch.Tensor,
+                    draft_len: torch.Tensor, tok: torch.Tensor, live: Optional[torch.Tensor] = None, eos: Optional[torch.Tensor] = None,
+                    vocab: int = 0, lookup: bool = True) -> None:
+    """vly_spec_rows_draft: ``spec_draft``'s rule per sequence over hist int32 [B, ctx_max] with ``pos[b] + len_add`` known tokens
+    -> draft int32 [B, k], draft_len int32 [B], tok int32 [B * (k + 1)].  ``live`` uint8 [B]: a sequence with live[b] == 0 gets
+    draft_len 0 and rows of token 0."""
+    k = _spec_k("spec_rows_draft", k)
+    if not 1 <= int(max_ngram) <= SPEC_MAX_NGRAM:
+        raise ValueError(f"spec_rows_draft: max_ngram must be in [1, {SPEC_MAX_NGRAM}], got {max_ngram}")
+    B = hist.shape[0] if hist.dim() == 2 else 0
+    _rows_tables("spec_rows_draft", B, k, hist, draft, draft_len, tok)
+    _rows_pos("spec_rows_draft", pos, B)
+    _rows_live("spec_rows_draft", live, B)
+    from . import lib_spec_rows
+    for t, name in ((hist, "hist"), (draft, "draft"), (draft_len, "draft_len"), (tok, "tok"), (pos, "pos")) + \
+            (((eos, "eos"),) if eos is not None else ()):
+        _chk(t, torch.int32, name)
+    if live is not None:
+        _chk(live, torch.uint8, "live")
+    rc = lib_spec_rows.load().vly_spec_rows_draft(hist.data_ptr(), hist.shape[1], pos.data_ptr(), int(len_add), _ptr(live), B, k,
+                                                  int(max_ngram), _ptr(eos), 0 if eos is None else eos.numel(), int(vocab),
+                                                  int(bool(lookup)), draft.data_ptr(), draft_len.data_ptr(), tok.data_ptr(), _stream())
+    lib_spec_rows.check(rc, "vly_spec_rows_draft")
+
+
+def spec_rows_accept(am: torch.Tensor, draft: torch.Tensor, draft_len: torch.Tensor, k: int, hist: torch.Tensor, pos: torch.Tensor,
+                     emit: torch.Tensor, tok: torch.Tensor, stats: torch.Tensor, live: Optional[torch.Tensor] = None) -> None:
+    """vly_spec_rows_accept: ``spec_accept`` per sequence — am int32 [B * (k + 1)], emit int32 [B, k + 2], stats int32 [B, 3];
+    tok[b * (k + 1)] = the sequence's next token, pos[b] += n_b + 1.  A sequence with live[b] == 0 gets emit[b, 0] = 0 and keeps
+    its position, history and counters."""
+    k = _spec_k("spec_rows_accept", k)
+    B = hist.shape[0] if hist.dim() == 2 else 0
+    _rows_tables("spec_rows_accept", B, k, hist, draft, draft_len, tok)
+    if am.numel() != B * (k + 1) or tuple(emit.shape) != (B, k + 2) or tuple(stats.shape) != (B, 3):
+        raise ValueError(f"spec_rows_accept: am [{B * (k + 1)}], emit [{B}, {k + 2}] and stats [{B}, 3] expected, got {tuple(am.shape)} / "
+                         f"{tuple(emit.shape)} / {tuple(stats.shape)}")
+    _rows_pos("spec_rows_accept", pos, B)
+    _rows_live("spec_rows_accept", live, B)
+    from . import lib_spec_rows
+    for t, name in ((am, "am"), (draft, "draft"), (draft_len, "draft_len"), (hist, "hist"), (pos, "pos"), (emit, "emit"), (tok, "tok"),
+                    (stats, "stats")):
+        _chk(t, torch.int32, name)
+    if live is not None:
+        _chk(live, torch.uint8, "live")
+    rc = lib_spec_rows.load().vly_spec_rows_accept(am.data_ptr(), draft.data_ptr(), draft_len.data_ptr(), _ptr(live), B, k, hist.data_ptr(),
+                                                   hist.shape[1], pos.data_ptr(), emit.data_ptr(), tok.data_ptr(), stats.data_ptr(), _stream())
+    lib_spec_rows.check(rc, "vly_spec_rows_accept")
+
+
+def spec_rows_counters(pos: torch.Tensor, k: int, ctx_max: int, out: torch.Tensor) -> torch.Tensor:
+    """vly_spec_rows_counters: out int32 [B * (k + 1)], out[b * (k + 1) + j] = pos[b] + j (the position clamped to
+    [0, ctx_max - 1]) — ``spec_counters`` per sequence, for ``argmax(..., ctr=out, ctr_add=1)`` over the step's rows."""
+    k = _spec_k("spec_rows_counters", k)
+    B = pos.numel() if isinstance(pos, torch.Tensor) else 0
+    _rows_pos("spec_rows_counters", pos, max(B, 1))
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or out.dim() != 1 or out.numel() != B * (k + 1):
+        raise ValueError(f"spec_rows_counters: out must be int32 [{B * (k + 1)}], got {getattr(out, 'dtype', type(out))} "
+                         f"{tuple(getattr(out, 'shape', ()))}")
+    if isinstance(ctx_max, bool) or int(ctx_max) < 1:
+        raise ValueError(f"spec_rows_counters: ctx_max must be >= 1, got {ctx_max}")
+    from . import lib_spec_rows
+    _chk(pos, torch.int32, "pos")
+    _chk(out, torch.int32, "out")
+    rc = lib_spec_rows.load().vly_spec_rows_counters(pos.data_ptr(), B, k, int(ctx_max), out.data_ptr(), _stream())
+    lib_spec_rows.check(rc, "vly_spec_rows_counters")
+    return out

@@ -110,7 +110,8 @@ class ContinuousBatcher:
     and ignored: the GEMV cost does not depend on the row count), clamped inside their cache rows."""
 
     def __init__(self, model, slots: int = 4, ctx_max: int = 1024, use_graph: bool = True, sampling: bool = False,
-                 processors: bool = False, eos_token_id=None, logprobs: Optional[int] = None):
+                 processors: bool = False, eos_token_id=None, logprobs: Optional[int] = None,
+                 prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None):
         """``sampling``: the captured step draws every slot's token with the parameters ``add`` gave its request
         (temperature, top-k, top-p, seed; DecodeSession ``sampling``) — a seeded request's tokens then depend on its seed
         alone, not on its slot or its neighbours.  Greedy requests take the argmax in either kind of batcher.
@@ -121,9 +122,38 @@ class ContinuousBatcher:
         (DecodeSession ``logprobs``).  ``add`` leaves the first token's in ``self.first_logprobs[slot]``, ``step`` the step's
         in ``self.last_logprobs`` — ``{slot: (lp, top ids, top lps)}`` — and the slot's row of ``self.sess.lp_table``
         (column = the token's index in the request's sequence) keeps them all.  A request's values do not depend on its slot
-        or its neighbours."""
+        or its neighbours.
+        ``prompt_lookup_num_tokens = k`` (1 <= k <= 7, slots x (k + 1) <= 8): prompt-lookup speculation for every slot in the one
+        captured step (valley_amd.spec.SpecRowsSession) — each slot drafts up to k tokens from its own history (its prompt, then
+        its tokens; ``max_matching_ngram_size``, default 2, in [1, 8]; a draft stops in front of ``eos_token_id``) and the step
+        verifies all slots' k + 1 rows at once.  ``step()`` then returns ``{slot: [t0, ...]}``, 1 .. k + 1 tokens per live slot:
+        exactly the tokens the plain batcher would have returned over as many steps (greedy, or the request's seed's under
+        ``sampling=True``, where a sampling request must bring its ``seed``).  EOS, stop criteria and max_new_tokens stay the
+        caller's business: the caller truncates a step's list at its own stop and releases the slot.  Not with ``processors``
+        or ``logprobs``.  ``speculation(slot)`` reports the slot's {"steps", "drafted", "accepted"}."""
         if not 1 <= slots <= 8:
             raise ValueError("1 <= slots <= 8 (the decode step streams weights with the GEMV kernels)")
+        self.spec_k = None
+        if prompt_lookup_num_tokens is None:
+            if max_matching_ngram_size is not None:
+                raise ValueError("max_matching_ngram_size needs prompt_lookup_num_tokens")
+        else:
+            k, n = prompt_lookup_num_tokens, 2 if max_matching_ngram_size is None else max_matching_ngram_size
+            if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= ops.SPEC_MAX_DRAFT:
+                raise ValueError(f"prompt_lookup_num_tokens must be an int in [1, {ops.SPEC_MAX_DRAFT}], got {k!r}")
+            if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= ops.SPEC_MAX_NGRAM:
+                raise ValueError(f"max_matching_ngram_size must be an int in [1, {ops.SPEC_MAX_NGRAM}], got {n!r}")
+            if slots * (k + 1) > ops.SPEC_MAX_QUERIES:
+                raise ValueError(f"speculation verifies slots x (k + 1) <= {ops.SPEC_MAX_QUERIES} rows per step: {slots} slots x "
+                                 f"(k + 1 = {k + 1}) = {slots * (k + 1)} rows")
+            if processors:
+                raise ValueError("prompt_lookup_num_tokens does not combine with processors=True (the logits processors run on "
+                                 "one row per sequence)")
+            if logprobs is not None:
+                raise ValueError("prompt_lookup_num_tokens does not combine with logprobs")
+            from . import spec as _spec
+            _spec.refuse_engine()
+            self.spec_k, self.spec_ngram = k, n
         self.model, self.ll = model, model.get_model().llama
         if ctx_max > self.ll.max_positions:
             # positions index the RoPE tables, which hold max_position_embeddings rows
@@ -135,8 +165,12 @@ class ContinuousBatcher:
         self.sampling = sampling
         self.processors = processors
         eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id])
-        self.sess = DecodeSession(self.ll, self.cache, use_graph=use_graph, per_row_positions=True, sampling=sampling,
-                                  processors=processors, processor_eos=eos, **({} if logprobs is None else {"logprobs": logprobs}))
+        if self.spec_k is not None:
+            self.sess = _spec.SpecRowsSession(self.ll, self.cache, self.spec_k, max_ngram=self.spec_ngram, eos_ids=eos,
+                                              use_graph=use_graph, sampling=sampling)
+        else:
+            self.sess = DecodeSession(self.ll, self.cache, use_graph=use_graph, per_row_positions=True, sampling=sampling,
+                                      processors=processors, processor_eos=eos, **({} if logprobs is None else {"logprobs": logprobs}))
         self.logprobs = None if logprobs is None else int(logprobs)
         self.first_logprobs, self.last_logprobs = {}, {}
         self.live = [False] * slots
@@ -159,6 +193,9 @@ class ContinuousBatcher:
             raise ValueError("add(temperature > 0) needs ContinuousBatcher(..., sampling=True)")
         params = None
         if self.sampling:
+            if seed is None and self.spec_k is not None and temperature >= ops.GREEDY_T:
+                raise ValueError("a sampling request of a speculating batcher needs its seed (add(..., seed=)): the drafts are "
+                                 "verified against the seed's own sequence")
             if seed is None:
                 seed = int(torch.randint(0, 1 << 62, (1,)).item()) if temperature >= ops.GREEDY_T else 0
             params = ops.sampling_rows(float(temperature), top_k, top_p, seed, device=self.ll.device)   # validates
@@ -199,10 +236,13 @@ class ContinuousBatcher:
             tok = int(ops.argmax(last, sampling=params, ctr_add=S)[0])
         else:
             tok = int(last[0].argmax())
-        if params is not None:
-            self.sess.sample[slot:slot + 1].copy_(params)
-        self.sess.pos[slot:slot + 1].fill_(S)
-        self.sess.tok[slot:slot + 1].fill_(tok)
+        if self.spec_k is not None:                              # the slot's history: the prompt, then the first token
+            self.sess.set_sequence(slot, S, tok, prompt_ids=ids[0], sampling_row=params)
+        else:
+            if params is not None:
+                self.sess.sample[slot:slot + 1].copy_(params)
+            self.sess.pos[slot:slot + 1].fill_(S)
+            self.sess.tok[slot:slot + 1].fill_(tok)
         if scored is not None:                                   # the first token sits at index S of the request's sequence
             raw, lse, tid, tl = scored
             tabs = None if not self.logprobs else tuple(t[slot:slot + 1] for t in self.sess.lp_top_tables)
@@ -215,7 +255,8 @@ class ContinuousBatcher:
 
     def step(self) -> dict:
         """One decode step for every live slot: feeds each slot's current token, returns {slot: next token} (greedy, or
-        drawn with the slot's parameters in a sampling batcher).  ``self.sess.logits[slot, :V]`` holds that slot's logits."""
+        drawn with the slot's parameters in a sampling batcher).  ``self.sess.logits[slot, :V]`` holds that slot's logits.
+        A speculating batcher returns {slot: [tokens]}, 1 .. k + 1 per live slot (the logits are then the verify step's rows)."""
         if not self._captured:
             self.sess.begin()
             self._captured = True
@@ -226,6 +267,11 @@ class ContinuousBatcher:
             self.release(i)
         if not any(self.live):
             return {}
+        if self.spec_k is not None:                              # one D2H read per step for all requests, here too
+            out = self.sess.step()
+            for i, toks in out.items():
+                self.length[i] += len(toks)
+            return out
         self.sess.step()
         toks = self.sess.tok.tolist()                            # one D2H read per step for all requests
         rows = None
@@ -255,4 +301,12 @@ class ContinuousBatcher:
     def release(self, slot: int) -> None:
         if self._captured and self.live[slot]:
             self.sess.check()                                    # once per leaving request (the step's D2H read has synchronised already)
+        if self.spec_k is not None and self.live[slot]:
+            self.sess.release(slot)
         self.live[slot] = False
+
+    def speculation(self, slot: int) -> dict:
+        """{"steps", "drafted", "accepted"} of the request in ``slot`` (a speculating batcher; kept until the slot is reused)."""
+        if self.spec_k is None:
+            raise ValueError("speculation() needs ContinuousBatcher(..., prompt_lookup_num_tokens=k)")
+        return self.sess.speculation(slot)

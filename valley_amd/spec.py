@@ -15,7 +15,11 @@ the host reads one small buffer per step (how many tokens, and which).
 Under seeded sampling (``sampling=True``) "argmax" reads "draw": row i draws, with the counter of the position it would occupy,
 the token plain seeded decoding draws there (a draw is a function of the logits, the seed and that counter), so the leading
 drafts that equal the draws of the rows before them are tokens of exactly the seed's sequence (ops.spec_counters -> ops.argmax
-with per-row counters in place of the plain argmax; DESIGN.md "seeded sampling")."""
+with per-row counters in place of the plain argmax; DESIGN.md "seeded sampling").
+
+``SpecRowsSession`` is the same step for several sequences at once — B sequences x (k + 1) rows <= 8, one position, history,
+draft and acceptance per sequence (ops.spec_rows_*, libvalley_hip_spec_rows.so) — the captured step of a speculating
+``ContinuousBatcher``."""
 from __future__ import annotations
 
 import os
@@ -40,6 +44,24 @@ def refuse_engine() -> None:
     if _decode.MERGE_IN == "oproj":
         raise ValueError("speculative decoding merges the attention's splits inside the attention launch: unset "
                          "VALLEY_DECODE_MERGE=oproj")
+
+
+def _norm_gemv(sess, gamma, w16, wq8, out, epilogue=ops.EPI_NONE):
+    """RMSNorm + projection of a verify step's ``sess.M`` rows through DecodeSession._enqueue_step's dispatch: the fused launch
+    where it takes the shape (two rows), the int8 / int4 forms on a quantized engine.  Shared by the two session classes."""
+    ll, M = sess.ll, sess.M
+    fused = _decode.FUSE_NORM and ops.gemv_rmsnorm_ok(M, ll.H)
+    if sess.wq and wq8 is not None:
+        if fused and sess.q_gemv_rmsnorm_ok(M, ll.H):
+            sess.q_gemv_rmsnorm(sess.h, gamma, ll.eps, *wq8, epilogue=epilogue, out=out)
+        else:
+            ops.rmsnorm(sess.h, gamma, ll.eps, out=sess.x)
+            sess.q_gemv(sess.x, *wq8, epilogue=epilogue, out=out)
+    elif fused:
+        ops.gemv_rmsnorm(sess.h, gamma, ll.eps, w16, epilogue=epilogue, out=out)
+    else:
+        ops.rmsnorm(sess.h, gamma, ll.eps, out=sess.x)
+        ops.gemv(sess.x, w16, epilogue=epilogue, out=out)
 
 
 class SpecDecodeSession:
@@ -94,23 +116,6 @@ class SpecDecodeSession:
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._gen = cache.generation
 
-    def _norm_gemv(self, gamma, w16, wq8, out, epilogue=ops.EPI_NONE):
-        """RMSNorm + projection through DecodeSession._enqueue_step's dispatch: the fused launch where it takes the shape
-        (k = 1: two rows), the int8 forms on a quantized engine."""
-        ll, M = self.ll, self.M
-        fused = _decode.FUSE_NORM and ops.gemv_rmsnorm_ok(M, ll.H)
-        if self.wq and wq8 is not None:
-            if fused and self.q_gemv_rmsnorm_ok(M, ll.H):
-                self.q_gemv_rmsnorm(self.h, gamma, ll.eps, *wq8, epilogue=epilogue, out=out)
-            else:
-                ops.rmsnorm(self.h, gamma, ll.eps, out=self.x)
-                self.q_gemv(self.x, *wq8, epilogue=epilogue, out=out)
-        elif fused:
-            ops.gemv_rmsnorm(self.h, gamma, ll.eps, w16, epilogue=epilogue, out=out)
-        else:
-            ops.rmsnorm(self.h, gamma, ll.eps, out=self.x)
-            ops.gemv(self.x, w16, epilogue=epilogue, out=out)
-
     def _enqueue_step(self):
         ll, c, M = self.ll, self.cache, self.M
         ops.spec_draft(self.hist, self.pos, 1, self.k, self.max_ngram, self.draft, self.draft_len, self.tok, eos=self.eos, vocab=ll.V,
@@ -118,7 +123,7 @@ class SpecDecodeSession:
         ops.embed_splice(self.tok, ll.embed, None, out=self.h)
         for li in range(ll.L):
             L = ll.layers[li]
-            self._norm_gemv(L["ln1"], L.get("w_qkv"), L.get("wq_qkv"), self.qkv)
+            _norm_gemv(self, L["ln1"], L.get("w_qkv"), L.get("wq_qkv"), self.qkv)
             # K / V of all k + 1 rows go into the cache at positions pos .. pos + k before anything is accepted.  The rows of
             # rejected drafts then lie AT or BEHIND the new position: no later query sees them (a query at P reads keys <= P,
             # and every position <= P has been rewritten by the step that fed its accepted token), and the next step's rope_kv
@@ -133,12 +138,12 @@ class SpecDecodeSession:
                 self.q_gemv(self.att, *L["wq_o"], residual=self.h, out=self.h)
             else:
                 ops.gemv(self.att, L["w_o"], residual=self.h, out=self.h)
-            self._norm_gemv(L["ln2"], L.get("w_gu"), L.get("wq_gu"), self.mlp, epilogue=ops.EPI_SWIGLU)
+            _norm_gemv(self, L["ln2"], L.get("w_gu"), L.get("wq_gu"), self.mlp, epilogue=ops.EPI_SWIGLU)
             if self.wq:
                 self.q_gemv(self.mlp, *L["wq_down"], residual=self.h, out=self.h)
             else:
                 ops.gemv(self.mlp, L["w_down"], residual=self.h, out=self.h)
-        self._norm_gemv(ll.norm, ll.lm_head, None, self.logits)
+        _norm_gemv(self, ll.norm, ll.lm_head, None, self.logits)
         if self.sample is None:
             ops.argmax(self.logits[:, :ll.V], out=self.am)
         else:                                                # row j: the draw of sequence index pos + j + 1
@@ -238,4 +243,180 @@ class SpecDecodeSession:
 
     def speculation(self) -> dict:
         s = self.stats.tolist()
+        return {"steps": s[0], "drafted": s[1], "accepted": s[2]}
+
+
+class SpecRowsSession:
+    """The verify step for SEVERAL sequences: ``cache.batch`` = B sequences x (k + 1) rows <= 8 rows in one captured step, every
+    sequence with its own position, history, draft and acceptance count (include/valley_hip_spec_rows.h) — the step of a
+    speculating ``ContinuousBatcher``.  SpecDecodeSession's step with M = B (k + 1) rows and the per-sequence kernels
+    (ops.spec_rows_*) in place of their single-sequence twins.
+
+    A row whose position lies behind its sequence's cache is dead (it stores nothing), and a draft never sits on one, so the
+    step runs at ANY position: a sequence near the end of its cache decodes its last tokens one per step inside the same graph.
+    A sequence that is not live (``self.live[b] == 0``) rides along: its rows are computed and ignored, and its position,
+    history and counters stay where they are."""
+
+    def __init__(self, llama: HipLlama, cache: HipKVCache, k: int, max_ngram: int = 2, eos_ids: Optional[Sequence[int]] = None,
+                 use_graph: bool = True, lookup: bool = True, sampling: bool = False):
+        """Arguments as SpecDecodeSession's.  ``lookup=False``: the caller writes ``self.draft`` [B, k] / ``self.draft_len`` [B]
+        before each ``step()``.  ``sampling``: row j of sequence b draws with ``self.sample[b * (k + 1) + j]`` (the sequence's
+        ops.sampling_rows row, replicated over its k + 1 rows by ``set_sequence``) and the counter pos[b] + j + 1."""
+        refuse_engine()
+        if not 1 <= int(k) <= ops.SPEC_MAX_DRAFT:
+            raise ValueError(f"k (prompt_lookup_num_tokens) must be in [1, {ops.SPEC_MAX_DRAFT}], got {k!r}")
+        if not 1 <= int(max_ngram) <= ops.SPEC_MAX_NGRAM:
+            raise ValueError(f"max_ngram (max_matching_ngram_size) must be in [1, {ops.SPEC_MAX_NGRAM}], got {max_ngram!r}")
+        B = cache.batch
+        if B * (int(k) + 1) > ops.SPEC_MAX_QUERIES:
+            raise ValueError(f"a SpecRowsSession verifies sequences x (k + 1) <= {ops.SPEC_MAX_QUERIES} rows per step: "
+                             f"{B} sequences x (k + 1 = {int(k) + 1}) = {B * (int(k) + 1)} rows")
+        if llama.heads * 128 != llama.H:
+            raise ValueError("speculative decoding needs head_dim 128")
+        self.ll, self.cache = llama, cache
+        self.B, self.k, self.S, self.M = B, int(k), int(k) + 1, B * (int(k) + 1)
+        self.max_ngram, self.lookup = int(max_ngram), bool(lookup)
+        mode = getattr(llama, "weight_quant", None)
+        self.wq = bool(mode)
+        self.q_gemv, self.q_gemv_rmsnorm, self.q_gemv_rmsnorm_ok = ops.quant_ops(mode)[1:] if mode else (None, None, None)
+        d, M, bf = llama.device, self.M, runtime.HALF
+        self.pos = torch.zeros((B,), dtype=torch.int32, device=d)          # position of each sequence's tok row 0
+        self.live = torch.zeros((B,), dtype=torch.uint8, device=d)
+        self.hist = torch.full((B, cache.ctx_max), -1, dtype=torch.int32, device=d)
+        self.tok = torch.zeros((M,), dtype=torch.int32, device=d)          # per sequence: the last token, then the draft
+        self.draft = torch.zeros((B, self.k), dtype=torch.int32, device=d)
+        self.draft_len = torch.zeros((B,), dtype=torch.int32, device=d)
+        self.emit = torch.zeros((B, self.k + 2), dtype=torch.int32, device=d)
+        self.stats = torch.zeros((B, 3), dtype=torch.int32, device=d)      # per sequence: steps, drafted, accepted
+        self.am = torch.zeros((M,), dtype=torch.int32, device=d)
+        self.sample = ops.sampling_rows([0.0] * M, device=d) if sampling else None
+        self.ctr = torch.zeros((M,), dtype=torch.int32, device=d) if sampling else None
+        self.eos = torch.tensor([int(e) for e in eos_ids], dtype=torch.int32, device=d) if eos_ids else None
+        self.h = torch.empty((M, llama.H), dtype=torch.float32, device=d)
+        self.x = torch.empty((M, llama.H), dtype=bf, device=d)
+        self.qkv = torch.empty((M, 3 * llama.H), dtype=bf, device=d)
+        self.att = torch.empty((M, llama.H), dtype=bf, device=d)
+        self.mlp = torch.empty((M, llama.I), dtype=bf, device=d)
+        self.logits = torch.empty((M, llama.Vpad), dtype=torch.float32, device=d)
+        self.scratch = ops.spec_rows_scratch(B, self.S, llama.heads, d)
+        self.use_graph = use_graph
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self._gen = cache.generation
+
+    def _enqueue_step(self):
+        ll, c, B, S = self.ll, self.cache, self.B, self.S
+        ops.spec_rows_draft(self.hist, self.pos, 1, self.k, self.max_ngram, self.draft, self.draft_len, self.tok, live=self.live,
+                            eos=self.eos, vocab=ll.V, lookup=self.lookup)
+        ops.embed_splice(self.tok, ll.embed, None, out=self.h)
+        for li in range(ll.L):
+            L = ll.layers[li]
+            _norm_gemv(self, L["ln1"], L.get("w_qkv"), L.get("wq_qkv"), self.qkv)
+            # as in SpecDecodeSession: the rows of rejected drafts lie at or behind the sequence's new position, unseen and then
+            # overwritten; dead rows (behind the cache's end) are not written at all
+            ops.spec_rows_rope_kv(self.qkv, c.k[li], c.v[li], ll.cos, ll.sin, B, S, ll.heads, self.pos)
+            ops.spec_rows_attention(self.qkv, c.k[li], c.v[li], c.key_valid, B, S, ll.heads, self.pos, self.scratch, out=self.att)
+            if self.wq:
+                self.q_gemv(self.att, *L["wq_o"], residual=self.h, out=self.h)
+            else:
+                ops.gemv(self.att, L["w_o"], residual=self.h, out=self.h)
+            _norm_gemv(self, L["ln2"], L.get("w_gu"), L.get("wq_gu"), self.mlp, epilogue=ops.EPI_SWIGLU)
+            if self.wq:
+                self.q_gemv(self.mlp, *L["wq_down"], residual=self.h, out=self.h)
+            else:
+                ops.gemv(self.mlp, L["w_down"], residual=self.h, out=self.h)
+        _norm_gemv(self, ll.norm, ll.lm_head, None, self.logits)
+        if self.sample is None:
+            ops.argmax(self.logits[:, :ll.V], out=self.am)
+        else:                                                # row j of sequence b: the draw of sequence index pos[b] + j + 1
+            ops.spec_rows_counters(self.pos, self.k, c.ctx_max, self.ctr)
+            ops.argmax(self.logits[:, :ll.V], sampling=self.sample, ctr=self.ctr, ctr_add=1, out=self.am)
+        ops.spec_rows_accept(self.am, self.draft, self.draft_len, self.k, self.hist, self.pos, self.emit, self.tok, self.stats,
+                             live=self.live)
+
+    def set_sequence(self, b: int, position: int, first_token: int, prompt_ids: Optional[torch.Tensor] = None, sampling_row=None):
+        """Sequence ``b`` starts (after its prefill filled ``position`` rows of its cache): its history is ``prompt_ids`` —
+        right-aligned in front of the position, as SpecDecodeSession.begin — followed by ``first_token``; its counters are zero,
+        it is live.  ``sampling_row``: its ops.sampling_rows row (a sampling session), replicated over its k + 1 rows."""
+        c, S = self.cache, self.S
+        if not 0 <= b < self.B:
+            raise ValueError(f"sequence {b} of {self.B}")
+        if not 0 <= position < c.ctx_max:
+            raise ValueError(f"position {position}: the first token's row must lie inside the cache's {c.ctx_max} positions")
+        self.hist[b].fill_(-1)
+        if prompt_ids is not None and position:
+            ids = prompt_ids.reshape(-1).to(torch.int32)[-position:]
+            self.hist[b, position - ids.numel():position].copy_(ids)
+        self.hist[b, position] = int(first_token)
+        self.pos[b] = position
+        self.tok[b * S:(b + 1) * S] = 0
+        self.tok[b * S] = int(first_token)
+        self.stats[b].zero_()
+        self.emit[b].zero_()
+        if sampling_row is not None:
+            if self.sample is None:
+                raise ValueError("set_sequence(sampling_row=...) needs SpecRowsSession(..., sampling=True)")
+            self.sample[b * S:(b + 1) * S].copy_(sampling_row.reshape(1, -1).expand(S, -1))
+        self.live[b] = 1
+
+    def release(self, b: int) -> None:
+        """Sequence ``b`` leaves: its rows ride along unread, from position 0 (an idle sequence reads one key block per step)."""
+        self.live[b] = 0
+        self.pos[b] = 0
+
+    def begin(self):
+        """Capture the step (once, or again when the cache's storage moved).  Any position will do: dead rows store nothing."""
+        if self.use_graph and (self.graph is None or self._gen != self.cache.generation):
+            self._capture()
+
+    def _capture(self):
+        """SpecDecodeSession._capture's scheme: a warm-up step on a side stream, the device-side state restored, ONE step
+        captured.  (The warm-up's K / V rows lie at and behind each sequence's position: the first real step overwrites them.)"""
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        state = [self.pos, self.tok, self.hist, self.stats, self.draft, self.draft_len, self.emit] + \
+            ([self.ctr] if self.ctr is not None else [])
+        saved = [t.clone() for t in state]
+        with torch.cuda.stream(s):
+            self._enqueue_step()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        for t, t0 in zip(state, saved):
+            t.copy_(t0)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._enqueue_step()
+        self.graph = g
+        self._gen = self.cache.generation
+
+    def check(self) -> None:
+        """Raise if the split attention's ticket counters are not back at zero (a launch that did not complete)."""
+        if int(self.scratch[1].abs().sum().item()) != 0:
+            self.scratch[1].zero_()
+            raise RuntimeError("vly_spec_rows_attention: ticket counters not at zero after a step (an attention launch did not "
+                               "complete); the step's output is invalid")
+
+    def step(self) -> dict:
+        """One verify step for every live sequence: ``{b: [tokens]}``, 1 .. k + 1 tokens each, from ONE device-to-host copy."""
+        c = self.cache
+        if c.key_valid is not None and c.key_valid.shape[1] != c.ctx_max:
+            raise RuntimeError("key_valid out of step with the cache")
+        if self.hist.shape[1] != c.ctx_max:
+            raise RuntimeError("the cache's depth changed under a SpecRowsSession: make a new session")
+        self.begin()
+        if self.use_graph:
+            self.graph.replay()
+        else:
+            self._enqueue_step()
+        out = {}
+        for b, row in enumerate(self.emit.tolist()):         # the step's one read: per sequence (n + 1, tokens, -1 ...)
+            n1 = row[0]
+            if n1 == 0:
+                continue
+            if not 1 <= n1 <= self.S:
+                raise RuntimeError(f"vly_spec_rows_accept reported {n1} tokens for a sequence of {self.S} rows")
+            out[b] = row[1:1 + n1]
+        return out
+
+    def speculation(self, b: int) -> dict:
+        s = self.stats[b].tolist()
         return {"steps": s[0], "drafted": s[1], "accepted": s[2]}
