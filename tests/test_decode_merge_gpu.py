@@ -70,6 +70,29 @@ def test_merge_in_attention_with_per_row_positions(monkeypatch):
         assert torch.equal(a[i][0], b[i][0]) and torch.equal(a[i][1], b[i][1]) and torch.equal(a[i][2], b[i][2]), i
 
 
+@pytest.mark.parametrize("M", [1, 2])
+@pytest.mark.parametrize("N", [6, 1001])
+@pytest.mark.parametrize("heads", [16, 40, 48])
+def test_attnmerge_gemv_is_exact(heads, N, M):
+    """vly_gemv_attnmerge_bf16 held to the truth (tests/gemv_oracle.py, MergeCase): partials with equal maxima and l = 0.5 in every
+    split and integer P·V sums merge to an x that is exact in 16 bits, and the o projection over it is exact: K = 2048, 5120, 6144
+    (both chunk counts of gemv_norm_kernel<.., PRO = 1>), fp32 out with bias + residual (a window of a wider buffer) and 16-bit out."""
+    from tests import gemv_oracle as G
+    from valley_amd import ops
+    from valley_amd.runtime import HALF
+    assert G.norm_plan(M, N, heads * 128, G.cu_count(), pro=1).kernel == f"gemv_norm_kernel<MR={M},CH={2 if heads <= 32 else 3},PRO=1>"
+    for has_b, has_r, od in ((True, True, torch.float32), (False, False, torch.float32), (True, False, HALF), (False, False, HALF)):
+        c = G.MergeCase(M, N, heads, 100 + heads + N + M, has_b, has_r)
+        part, w = c.partials.cuda(), c.w.cuda()
+        b = c.bias.cuda() if has_b else None
+        r = G.res_window(c.res.cuda()) if has_r else None
+        what = f"gemv_attnmerge M={M} {N}x{heads * 128} bias {has_b} residual {has_r} out {od}"
+        buf, out, _ = G.window(M, N, od)
+        ops.gemv_attnmerge(part, w, b, r, od, out)
+        G.assert_exact(out, c.truth, what)
+        G.assert_guards(buf, M, N, what)
+
+
 def test_merged_entry_point_rejects_bad_arguments():
     from valley_amd import lib
     L = lib.load()
