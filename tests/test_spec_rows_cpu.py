@@ -37,9 +37,10 @@ def test_the_rows_table_sits_beside_the_seven():
     # editing anything the unit includes recompiles it; the shared attention is a dependency of both libraries that instantiate it
     src = open(os.path.join(build.CSRC, "spec_rows.hip")).read()
     included = set(re.findall(r'#include "([a-z0-9_]+\.(?:hpp|inc))"', src))
-    assert included <= set(c.deps) | set(build.COMPANION_SHARED) and "spec_attn.inc" in included
+    assert included <= set(c.deps) | set(build.COMPANION_SHARED) and {"spec_attn.inc", "spec_lookup.inc"} <= included
     spec = next(x for x in build.COMPANIONS if x.name == "spec")
-    assert "spec_attn.inc" in spec.deps and "spec_attn.inc" in c.deps
+    for inc in ("spec_attn.inc", "spec_lookup.inc"):             # ... and the draft and acceptance rules likewise
+        assert inc in spec.deps and inc in c.deps and f'#include "{inc}"' in open(os.path.join(build.CSRC, "spec.hip")).read()
     # objects land under lib/spec_rows/, which .gitignore covers with the rest of the library directory
     assert "valley_amd/lib/" in open(os.path.join(ROOT, ".gitignore")).read().split()
 

@@ -4,7 +4,8 @@ ContinuousBatcher(prompt_lookup_num_tokens=k)):
 * vly_spec_rows_attention and vly_spec_rows_rope_kv bit for bit against vly_spec_attention / vly_rope_kv of each sequence alone,
   the attention's independence of S, of the sequence's index and of its neighbours' positions, and dead rows (positions behind the
   cache's end) that store nothing;
-* vly_spec_rows_draft, _accept and _counters against tests/spec_rows_ref.py, exactly;
+* vly_spec_rows_draft, _accept and _counters against tests/spec_rows_ref.py, exactly, and the draft and the acceptance of ONE
+  sequence against vly_spec_draft / vly_spec_accept on the same tables, buffer for buffer (both call csrc/spec_lookup.inc);
 * SpecRowsSession with forced drafts against SpecDecodeSession of each sequence alone, and the speculating batcher against the
   plain one, token for token (greedy and seeded).
 
@@ -337,6 +338,89 @@ def test_counters_rows():
         ops.spec_rows_counters(pos_tensor(pos), k, CTX, view)
         guards_intact({"ctr": (t, view)})
         assert view.tolist() == RR.counters(pos, k, CTX), (pos, k)
+
+
+# ---- one sequence: the rows kernels against the single-sequence kernels (both call csrc/spec_lookup.inc) ---------------------------
+WIDE = 1030                                                      # columns: a thread's second window start (t + 1024) exists
+
+
+def twin_draft(hist, length, k, n, eos=(), vocab=0, lookup=True, len_add=1):
+    """vly_spec_rows_draft at B = 1 and vly_spec_draft on the same tables: every output buffer equal, and equal to the reference."""
+    from valley_amd import ops
+    hist = np.asarray(hist).reshape(1, -1)
+    before_d, before_dl = np.arange(50, 50 + k), [9]
+    e = torch.tensor(list(eos), dtype=torch.int32, device=DEV) if len(eos) else None
+    out = []
+    for rows in (True, False):
+        bufs = {"hist": guarded(hist if rows else hist[0]), "pos": guarded([length - len_add]),
+                "draft": guarded(before_d.reshape(1, k) if rows else before_d), "dl": guarded(before_dl), "tok": guarded(np.full((k + 1,), -5))}
+        fn = ops.spec_rows_draft if rows else ops.spec_draft
+        fn(bufs["hist"][1], bufs["pos"][1], len_add, k, n, bufs["draft"][1], bufs["dl"][1], bufs["tok"][1], eos=e, vocab=vocab, lookup=lookup)
+        guards_intact(bufs)
+        assert bufs["hist"][1].reshape(-1).tolist() == hist[0].tolist() and bufs["pos"][1].tolist() == [length - len_add]
+        out.append({name: bufs[name][1].reshape(-1).tolist() for name in ("draft", "dl", "tok")})
+    d, dl, tok = RR.draft_rows(hist, [length], k, n, eos, vocab=vocab, lookup=lookup, draft=before_d, draft_len=before_dl)
+    want = {"draft": d[0], "dl": dl, "tok": tok[0]}
+    assert out[0] == out[1] == want, (length, k, n, eos, vocab, lookup, len_add, out, want)
+    return want
+
+
+def test_rows_draft_of_one_sequence_is_the_single_sequence_draft():
+    g = np.random.default_rng(11)
+    dense = g.integers(0, 4, size=WIDE)                          # four ids: every n-gram size finds a match early
+    for length in (1, 2, 1029, 1030):
+        for k in (1, 7):
+            for n in (1, 8):
+                twin_draft(dense, length, k, n)
+                twin_draft(dense, length, k, n, eos=(3,))
+    twin_draft(dense, 1029, 7, 8, len_add=2)
+    for length in (1029, 1030):                                  # the caller's draft (9 tokens claimed), capped at the cache's end
+        assert twin_draft(dense, length, 7, 8, lookup=False)["tok"][1:] == [50] * (WIDE - length) + [int(dense[length - 1])] * (7 - (WIDE - length))
+    # one match, at a window start >= 1024: only the second round of the search (t + 1024) finds it
+    # (1029 of 1030 columns known: the end of the cache leaves room for one drafted token)
+    far = np.arange(1000, 1000 + WIDE)
+    far[1024:1026] = far[1027:1029] = [11, 12]
+    for k in (1, 7):
+        for n in (8, 1):                                         # [11, 12] at start 1024; the 1-gram [12] at start 1025
+            assert twin_draft(far, 1029, k, n) == {"draft": [2026] + [12] * (k - 1), "dl": [1], "tok": [12, 2026] + [12] * (k - 1)}
+    assert twin_draft(far, 1030, 7, 8)["dl"] == [0]              # the sequence ends on [11, 12, 2029]: nothing matches
+    # ... and the same n-gram at a start < 1024 as well: the earlier one wins
+    both = far.copy()
+    both[50:52] = [11, 12]
+    assert twin_draft(both, 1029, 7, 8)["tok"] == [12, 1052] + [12] * 6
+    assert twin_draft(both, 1029, 7, 8, eos=(2026,))["dl"] == [1]
+    assert twin_draft(both, 1029, 7, 8, eos=(1052,)) == {"draft": [12] * 7, "dl": [0], "tok": [12] * 8}       # cropped by an EOS
+    assert twin_draft(both, 1029, 7, 8, vocab=1053)["dl"] == [1]
+    assert twin_draft(both, 1029, 7, 8, vocab=1052)["tok"] == [12] * 8                                        # ... by the vocabulary
+
+
+def test_rows_accept_of_one_sequence_is_the_single_sequence_accept():
+    from valley_amd import ops
+    k = 3
+    am = np.array([10, 11, 12, 13])
+    pairs = 0
+    for pos in (0, 19, 20, 21, 22, 23):                          # hist has 24 columns: drafts wholly, partly, not at all inside
+        for dl in range(k + 1):
+            for m in range(dl + 1):                              # the first wrong draft: m of dl accepted
+                draft = np.array([a if i != m else 99 for i, a in enumerate(am[:k])])
+                hist, stats = np.full((1, 24), -7), np.array([[3, 4, 5]])
+                out = []
+                for rows in (True, False):
+                    flat = (lambda a: a) if rows else (lambda a: np.asarray(a).reshape(-1))
+                    bufs = {"am": guarded(am), "draft": guarded(flat(draft.reshape(1, k))), "dl": guarded([dl]), "hist": guarded(flat(hist)),
+                            "pos": guarded([pos]), "emit": guarded(flat(np.full((1, k + 2), -3))), "tok": guarded(np.full((k + 1,), -3)),
+                            "stats": guarded(flat(stats))}
+                    fn = ops.spec_rows_accept if rows else ops.spec_accept
+                    fn(*(bufs[name][1] for name in ("am", "draft", "dl")), k, *(bufs[name][1] for name in ("hist", "pos", "emit", "tok", "stats")))
+                    guards_intact(bufs)
+                    assert bufs["am"][1].tolist() == am.tolist() and bufs["draft"][1].reshape(-1).tolist() == draft.tolist() and bufs["dl"][1].tolist() == [dl]
+                    out.append({name: bufs[name][1].reshape(-1).tolist() for name in ("hist", "emit", "tok", "stats", "pos")})
+                ns, h, emit, tok, st, p = RR.accept_rows(am, draft, [dl], k, hist, [pos], stats, emit=np.full((1, k + 2), -3), tok=[-3] * (k + 1))
+                want = {"hist": h.reshape(-1).tolist(), "emit": emit[0], "tok": tok, "stats": st[0], "pos": p}
+                assert out[0] == out[1] == want, (pos, dl, m, out, want)
+                assert ns[0] == min(m, max(0, 24 - (pos + 1))) and want["tok"][0] == am[ns[0]]
+                pairs += 1
+    assert pairs == 6 * 10
 
 
 # ---- the session ---------------------------------------------------------------------------------------------------------------

@@ -43,19 +43,21 @@ class Companion(NamedTuple):
 
 # beam_rows.inc: the row top-K and merge of the beam and logits companions and the log-sum-exp the score companion shares with them;
 # qgemv.hpp: the GEMV skeleton the two weight-only formats share; spec_attn.inc: the split attention of a verify step, which the
-# single-sequence companion and the per-sequence one (COMPANIONS_ROWS) instantiate with their own position source
+# single-sequence companion and the per-sequence one (COMPANIONS_ROWS) instantiate with their own position source; spec_lookup.inc:
+# the draft and acceptance rules of one sequence, which the draft / accept kernels of the same two call on their own tables
 COMPANIONS = (
     Companion("beam", LIB_BEAM, ("beam.hip",), "valley_hip_beam.h", ("beam_rows.inc",)),
     Companion("logits", LIB_LOGITS, ("logits.hip",), "valley_hip_logits.h", ("beam_rows.inc",)),
     Companion("wq", LIB_WQ, ("wq.hip",), "valley_hip_wq.h", ("common.hpp", "qgemv.hpp")),
     Companion("score", LIB_SCORE, ("score.hip",), "valley_hip_score.h", ("beam_rows.inc",)),
-    Companion("spec", LIB_SPEC, ("spec.hip",), "valley_hip_spec.h", ("common.hpp", "spec_attn.inc")),
+    Companion("spec", LIB_SPEC, ("spec.hip",), "valley_hip_spec.h", ("common.hpp", "spec_attn.inc", "spec_lookup.inc")),
     Companion("w4", LIB_W4, ("w4.hip",), "valley_hip_w4.h", ("common.hpp", "qgemv.hpp")),
     Companion("spec_sample", LIB_SPEC_SAMPLE, ("spec_sample.hip",), "valley_hip_spec_sample.h", ()),
 )
 # batched speculation: a table of its own, walked by the same code (the seven above are what the other libraries' tests count)
 COMPANIONS_ROWS = (
-    Companion("spec_rows", LIB_SPEC_ROWS, ("spec_rows.hip",), "valley_hip_spec_rows.h", ("common.hpp", "spec_attn.inc")),
+    Companion("spec_rows", LIB_SPEC_ROWS, ("spec_rows.hip",), "valley_hip_spec_rows.h",
+              ("common.hpp", "spec_attn.inc", "spec_lookup.inc")),
 )
 SOURCES = ["capi.hip", "gemm_bf16.hip", "gemm_p32.hip", "gemm_p16.hip", "gemm_streamk.hip", "norm_elementwise.hip", "attention.hip", "temporal_delta.hip", "preprocess.hip", "gemv_bf16.hip", "precise_f32.hip", "gemm_skinny.hip", "decode_step.hip", "sampling.hip"]
 

@@ -1,5 +1,7 @@
 // libvalley_hip_spec.so (include/valley_hip_spec.h): prompt-lookup speculative decoding on gfx950 — the split attention of the
-// verify step's k + 1 queries, the draft lookup and the acceptance.
+// verify step's k + 1 queries, the draft lookup and the acceptance.  The attention kernel lives in spec_attn.inc and the draft and
+// acceptance rules in spec_lookup.inc, both shared with spec_rows.hip: the kernels here say where the ONE sequence's tables and
+// position are.
 //
 // The attention is decode_split_kernel's idea (attention.hip) for a few queries of ONE sequence: a head's keys are streamed
 // once, by four workgroups, for all S queries.  What differs is the key partition.  decode_split_kernel cuts [0, kv_len) into
@@ -26,79 +28,18 @@ namespace {
 
 #include "spec_attn.inc"      // the attention kernel, shared with spec_rows.hip (ROWS = false here: one position per launch)
 static_assert(SPLITS == VLY_SPEC_SPLITS && PART == VLY_SPEC_PARTIAL, "spec_attn.inc and valley_hip_spec.h disagree");
+#include "spec_lookup.inc"    // the draft and acceptance rules of one sequence, shared with spec_rows.hip
+static_assert(MAX_NGRAM == VLY_SPEC_MAX_NGRAM, "spec_lookup.inc and valley_hip_spec.h disagree");
 
 // ---- vly_spec_draft ---------------------------------------------------------------------------------------------------------
-// One workgroup of 1024 threads.  For each n-gram size, largest first, thread t tests the window starts t, t + 1024, ... in
-// ascending order and keeps its first hit; the earliest hit of the block is a minimum over the waves' minima (no atomics).
+// One workgroup of 1024 threads over the one sequence: lookup_draft with the length clamped into the history.
 __global__ void __launch_bounds__(1024) spec_draft_kernel(const int32_t* __restrict__ hist, int ctx_max, const int32_t* __restrict__ len_dev,
                                                           int len_add, int k, int max_ngram, const int32_t* __restrict__ eos, int n_eos,
                                                           int vocab, int lookup, int32_t* __restrict__ draft, int32_t* __restrict__ draft_len,
                                                           int32_t* __restrict__ tok) {
     __shared__ int red[16];
-    const int tid = threadIdx.x;
     const int len = max(1, min((len_dev ? len_dev[0] : 0) + len_add, ctx_max));
-    const int last = hist[len - 1];
-    const int cap = min(k, ctx_max - len);                       // the verify step's last real position stays inside the cache
-    if (!lookup) {
-        if (tid == 0) {
-            const int dl = max(0, min(draft_len[0], cap));
-            tok[0] = last;
-            for (int i = 0; i < k; ++i) tok[1 + i] = i < dl ? draft[i] : last;
-        }
-        return;
-    }
-    int start = -1;                                              // first token of the continuation, -1: no match
-    for (int n = min(max_ngram, len - 1); n >= 1; --n) {
-        int tl[VLY_SPEC_MAX_NGRAM];
-#pragma unroll
-        for (int d = 0; d < VLY_SPEC_MAX_NGRAM; ++d) tl[d] = d < n ? hist[len - n + d] : 0;
-        int best = INT_MAX;
-        for (int i = tid; i < len - n; i += 1024) {              // i + n - 1 <= len - 2: columns from len on are never read
-            bool m = true;
-#pragma unroll
-            for (int d = 0; d < VLY_SPEC_MAX_NGRAM; ++d)
-                if (d < n) m = m && hist[i + d] == tl[d];
-            if (m) {
-                best = i;
-                break;
-            }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) best = min(best, __shfl_xor(best, off, 64));
-        __syncthreads();                                         // red: the previous size's minima have been read
-        if ((tid & 63) == 0) red[tid >> 6] = best;
-        __syncthreads();
-        best = red[0];
-#pragma unroll
-        for (int w = 1; w < 16; ++w) best = min(best, red[w]);
-        if (best != INT_MAX) {                                   // (uniform) the first size with a match decides
-            start = best + n;
-            break;
-        }
-    }
-    if (tid != 0) return;
-    int dl = 0;
-    if (start >= 0) {
-        dl = min(start + k, len) - start;
-        for (int j = 0; j < dl; ++j) {                           // cropped in front of the first EOS (or unusable id)
-            const int t = hist[start + j];
-            bool stop = t < 0 || (vocab > 0 && t >= vocab);
-            for (int e = 0; e < n_eos; ++e) stop = stop || t == eos[e];
-            if (stop) {
-                dl = j;
-                break;
-            }
-        }
-        dl = min(dl, cap);
-    }
-    dl = max(dl, 0);
-    tok[0] = last;
-    for (int j = 0; j < k; ++j) {
-        const int t = j < dl ? hist[start + j] : last;
-        draft[j] = t;
-        tok[1 + j] = t;
-    }
-    draft_len[0] = dl;
+    lookup_draft(hist, ctx_max, len, k, max_ngram, eos, n_eos, vocab, lookup, draft, draft_len, tok, red);
 }
 
 // ---- vly_spec_accept --------------------------------------------------------------------------------------------------------
@@ -107,23 +48,7 @@ __global__ void __launch_bounds__(64) spec_accept_kernel(const int32_t* __restri
                                                          int ctx_max, int32_t* __restrict__ pos_dev, int32_t* __restrict__ emit,
                                                          int32_t* __restrict__ tok, int32_t* __restrict__ stats) {
     if (threadIdx.x != 0) return;
-    const int pos = pos_dev[0];
-    // vly_spec_draft's clamp (len = pos + 1): the rows behind it were fed the last token, not the draft, and are not compared
-    const long room = (long)ctx_max - ((long)pos + 1);
-    const int dl = (int)max(0L, min((long)min(draft_len[0], k), room));
-    int n = 0;
-    while (n < dl && draft[n] == am[n]) ++n;
-    emit[0] = n + 1;
-    for (int j = 0; j <= k; ++j) emit[1 + j] = j <= n ? am[j] : -1;
-    for (int j = 0; j <= n; ++j) {
-        const long c = (long)pos + 1 + j;
-        if (c >= 0 && c < ctx_max) hist[c] = am[j];
-    }
-    tok[0] = am[n];
-    stats[0] += 1;
-    stats[1] += dl;
-    stats[2] += n;
-    pos_dev[0] = pos + n + 1;
+    lookup_accept(am, draft, draft_len, k, hist, ctx_max, pos_dev, emit, tok, stats);
 }
 
 template <int DT>

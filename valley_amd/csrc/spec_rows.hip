@@ -5,7 +5,8 @@
 // What is new against the single-sequence kernels is only where a row's position comes from (pos_rows[b] + j) and what happens
 // at the end of a sequence's cache: a row whose position lies behind it is DEAD — it stores nothing — where the single-sequence
 // kernels move the whole step back by clamping the position to ctx_max - S.  The attention is spec.hip's kernel itself
-// (spec_attn.inc, ROWS = true); the RoPE restates rope_kv_kernel (norm_elementwise.hip) on the dtype code, since a companion
+// (spec_attn.inc, ROWS = true), the draft and the acceptance are spec.hip's rules themselves (spec_lookup.inc) on one sequence's
+// row of every table, behind the test for an idle slot; the RoPE restates rope_kv_kernel (norm_elementwise.hip) on the dtype code, since a companion
 // cannot link the main library: same loads, same rope_rot, same packing, and tests/test_spec_rows_gpu.py compares the bits.
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -19,6 +20,8 @@ namespace {
 
 #include "spec_attn.inc"      // the attention kernel, shared with spec.hip (ROWS = true here: one position per sequence)
 static_assert(SPLITS == VLY_SPEC_ROWS_SPLITS && PART == VLY_SPEC_ROWS_PARTIAL, "spec_attn.inc and valley_hip_spec_rows.h disagree");
+#include "spec_lookup.inc"    // the draft and acceptance rules of one sequence, shared with spec.hip
+static_assert(MAX_NGRAM == VLY_SPEC_ROWS_MAX_NGRAM, "spec_lookup.inc and valley_hip_spec_rows.h disagree");
 
 VLY_DEVICE int row_pos(const int32_t* __restrict__ pos_rows, int b, int ctx_max) { return max(0, min(pos_rows[b], ctx_max - 1)); }
 
@@ -68,8 +71,7 @@ __global__ void __launch_bounds__(256) rows_rope_kv_kernel(uint16_t* __restrict_
 }
 
 // ---- vly_spec_rows_draft ----------------------------------------------------------------------------------------------------
-// spec_draft_kernel (spec.hip) with blockIdx.x = the sequence: 1024 threads, thread t tests the window starts t, t + 1024, ... of
-// its sequence's history in ascending order; the earliest hit is a minimum over the waves' minima (no atomics).
+// lookup_draft (spec_lookup.inc) with blockIdx.x = the sequence: 1024 threads over that sequence's row of every table.
 __global__ void __launch_bounds__(1024) rows_draft_kernel(const int32_t* __restrict__ hist_all, int ctx_max, const int32_t* __restrict__ pos_rows,
                                                           int len_add, const uint8_t* __restrict__ live, int k, int max_ngram,
                                                           const int32_t* __restrict__ eos, int n_eos, int vocab, int lookup,
@@ -86,72 +88,11 @@ __global__ void __launch_bounds__(1024) rows_draft_kernel(const int32_t* __restr
         return;
     }
     const int len = max(1, min(pos_rows[b] + len_add, ctx_max));
-    const int last = hist[len - 1];
-    const int cap = min(k, ctx_max - len);                       // drafts sit on live rows only
-    if (!lookup) {
-        if (tid == 0) {
-            const int dl = max(0, min(draft_len[b], cap));
-            tok[0] = last;
-            for (int i = 0; i < k; ++i) tok[1 + i] = i < dl ? draft[i] : last;
-        }
-        return;
-    }
-    int start = -1;                                              // first token of the continuation, -1: no match
-    for (int n = min(max_ngram, len - 1); n >= 1; --n) {
-        int tl[VLY_SPEC_ROWS_MAX_NGRAM];
-#pragma unroll
-        for (int d = 0; d < VLY_SPEC_ROWS_MAX_NGRAM; ++d) tl[d] = d < n ? hist[len - n + d] : 0;
-        int best = INT_MAX;
-        for (int i = tid; i < len - n; i += 1024) {              // i + n - 1 <= len - 2: columns from len on are never read
-            bool m = true;
-#pragma unroll
-            for (int d = 0; d < VLY_SPEC_ROWS_MAX_NGRAM; ++d)
-                if (d < n) m = m && hist[i + d] == tl[d];
-            if (m) {
-                best = i;
-                break;
-            }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) best = min(best, __shfl_xor(best, off, 64));
-        __syncthreads();                                         // red: the previous size's minima have been read
-        if ((tid & 63) == 0) red[tid >> 6] = best;
-        __syncthreads();
-        best = red[0];
-#pragma unroll
-        for (int w = 1; w < 16; ++w) best = min(best, red[w]);
-        if (best != INT_MAX) {                                   // (uniform) the first size with a match decides
-            start = best + n;
-            break;
-        }
-    }
-    if (tid != 0) return;
-    int dl = 0;
-    if (start >= 0) {
-        dl = min(start + k, len) - start;
-        for (int j = 0; j < dl; ++j) {                           // cropped in front of the first EOS (or unusable id)
-            const int t = hist[start + j];
-            bool stop = t < 0 || (vocab > 0 && t >= vocab);
-            for (int e = 0; e < n_eos; ++e) stop = stop || t == eos[e];
-            if (stop) {
-                dl = j;
-                break;
-            }
-        }
-        dl = min(dl, cap);
-    }
-    dl = max(dl, 0);
-    tok[0] = last;
-    for (int j = 0; j < k; ++j) {
-        const int t = j < dl ? hist[start + j] : last;
-        draft[j] = t;
-        tok[1 + j] = t;
-    }
-    draft_len[b] = dl;
+    lookup_draft(hist, ctx_max, len, k, max_ngram, eos, n_eos, vocab, lookup, draft, draft_len + b, tok, red);   // drafts sit on live rows only
 }
 
 // ---- vly_spec_rows_accept ---------------------------------------------------------------------------------------------------
-// one thread per sequence; every table row it writes is its own sequence's
+// one thread per sequence (lookup_accept, spec_lookup.inc); every table row it writes is its own sequence's
 __global__ void __launch_bounds__(64) rows_accept_kernel(const int32_t* __restrict__ am_all, const int32_t* __restrict__ draft_all,
                                                          const int32_t* __restrict__ draft_len, const uint8_t* __restrict__ live, int B, int k,
                                                          int32_t* __restrict__ hist_all, int ctx_max, int32_t* __restrict__ pos_rows,
@@ -162,27 +103,8 @@ __global__ void __launch_bounds__(64) rows_accept_kernel(const int32_t* __restri
             emit[0] = 0;
             continue;
         }
-        const int32_t* am = am_all + (size_t)b * (k + 1);
-        const int32_t* draft = draft_all + (size_t)b * k;
-        int32_t* hist = hist_all + (size_t)b * ctx_max;
-        int32_t* stats = stats_all + (size_t)b * 3;
-        const int pos = pos_rows[b];
-        // vly_spec_rows_draft's cap (len = pos + 1): the rows behind it were fed the last token, not the draft, and are not compared
-        const long room = (long)ctx_max - ((long)pos + 1);
-        const int dl = (int)max(0L, min((long)min(draft_len[b], k), room));
-        int n = 0;
-        while (n < dl && draft[n] == am[n]) ++n;
-        emit[0] = n + 1;
-        for (int j = 0; j <= k; ++j) emit[1 + j] = j <= n ? am[j] : -1;
-        for (int j = 0; j <= n; ++j) {
-            const long c = (long)pos + 1 + j;
-            if (c >= 0 && c < ctx_max) hist[c] = am[j];
-        }
-        tok[(size_t)b * (k + 1)] = am[n];
-        stats[0] += 1;
-        stats[1] += dl;
-        stats[2] += n;
-        pos_rows[b] = pos + n + 1;
+        lookup_accept(am_all + (size_t)b * (k + 1), draft_all + (size_t)b * k, draft_len + b, k, hist_all + (size_t)b * ctx_max, ctx_max,
+                      pos_rows + b, emit, tok + (size_t)b * (k + 1), stats_all + (size_t)b * 3);
     }
 }
 

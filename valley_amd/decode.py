@@ -36,6 +36,35 @@ PERSISTENT = os.environ.get("VALLEY_DECODE_PERSISTENT", "0") != "0"
 MERGE_IN = os.environ.get("VALLEY_DECODE_MERGE", "attn")
 SPLIT_ROWS = os.environ.get("VALLEY_DECODE_SPLIT_ROWS", "1") != "0"       # round 5: the merged split attention for 3 .. 8 rows as well
 
+
+def _norm_gemv(sess, gamma, w16, wq, out, epilogue=ops.EPI_NONE):
+    """RMSNorm + projection of a step's ``sess.M`` rows of ``sess.h`` — THE norm -> projection dispatch of DecodeSession and of the
+    verify steps (spec.py): one launch where the fused kernel takes the shape (bit-identical either way; VALLEY_DECODE_FUSE_NORM=0
+    keeps the pairs, for A/B runs), the int8 / int4 forms where the engine is quantized and the seam has a quantized weight ``wq``
+    (the lm_head has none)."""
+    ll, M = sess.ll, sess.M
+    fused = FUSE_NORM and ops.gemv_rmsnorm_ok(M, ll.H)
+    if sess.wq and wq is not None:
+        if fused and sess.q_gemv_rmsnorm_ok(M, ll.H):
+            sess.q_gemv_rmsnorm(sess.h, gamma, ll.eps, *wq, epilogue=epilogue, out=out)
+        else:
+            ops.rmsnorm(sess.h, gamma, ll.eps, out=sess.x)
+            sess.q_gemv(sess.x, *wq, epilogue=epilogue, out=out)
+    elif fused:
+        ops.gemv_rmsnorm(sess.h, gamma, ll.eps, w16, epilogue=epilogue, out=out)
+    else:
+        ops.rmsnorm(sess.h, gamma, ll.eps, out=sess.x)
+        ops.gemv(sess.x, w16, epilogue=epilogue, out=out)
+
+
+def _gemv_residual(sess, a, L, name):
+    """h += a @ W^T for the layer's ``o`` or ``down`` projection, over the engine's weight format."""
+    if sess.wq:
+        sess.q_gemv(a, *L["wq_" + name], residual=sess.h, out=sess.h)
+    else:
+        ops.gemv(a, L["w_" + name], residual=sess.h, out=sess.h)
+
+
 class DecodeSession:
     def __init__(self, llama: HipLlama, cache: HipKVCache, use_graph: bool = True, per_row_positions: bool = False,
                  sampling: bool = False, beams: Optional[tuple] = None, processors: bool = False,
@@ -70,7 +99,7 @@ class DecodeSession:
         B, d = cache.batch, llama.device
         if B > 8:
             raise ValueError("decode sessions stream weights with the GEMV kernel: batch <= 8")
-        self.B = B
+        self.B = self.M = B                                      # M: the step's rows (_norm_gemv)
         if logprobs is not None:
             if beams is not None:
                 raise ValueError("beam sessions take no logprobs: beam search reports sequences_scores")
@@ -151,10 +180,6 @@ class DecodeSession:
     def _enqueue_step(self):
         ll, c = self.ll, self.cache
         B = self.B
-        # the three norm -> projection seams as one launch each where the fused kernel takes the shape (bit-identical either way;
-        # VALLEY_DECODE_FUSE_NORM=0 keeps the pairs, for A/B runs)
-        fused = FUSE_NORM and ops.gemv_rmsnorm_ok(B, ll.H)
-        wq, wq_fused = self.wq, self.wq and fused and self.q_gemv_rmsnorm_ok(B, ll.H)
         # every head over four workgroups.  Merged inside the attention launch (the default) it does not depend on the o GEMV's form, so
         # three to eight rows take it too: at eight requests decode_fused_kernel's 320 workgroups of 512 threads are 1.25 rounds of one
         # workgroup per CU (23 us per layer, 15 % of the step); 1280 quarter-head workgroups stream the same K / V evenly
@@ -169,21 +194,12 @@ class DecodeSession:
                               self.per_row, ll.heads, ll.I, ll.eps, c.ctx_max, self.sync)
         for li in range(0 if self.persistent else ll.L):
             L = ll.layers[li]
-            if wq_fused:
-                self.q_gemv_rmsnorm(self.h, L["ln1"], ll.eps, *L["wq_qkv"], out=self.qkv)
-            elif wq:
-                ops.rmsnorm(self.h, L["ln1"], ll.eps, out=self.x)
-                self.q_gemv(self.x, *L["wq_qkv"], out=self.qkv)
-            elif fused:
-                ops.gemv_rmsnorm(self.h, L["ln1"], ll.eps, L["w_qkv"], out=self.qkv)      # input_layernorm inside the q|k|v GEMV
-            else:
-                ops.rmsnorm(self.h, L["ln1"], ll.eps, out=self.x)
-                ops.gemv(self.x, L["w_qkv"], out=self.qkv)
+            _norm_gemv(self, L["ln1"], L.get("w_qkv"), L.get("wq_qkv"), self.qkv)      # input_layernorm (inside) the q|k|v GEMV
             if split:                                            # every head over four workgroups; the o GEMV merges
                 if MERGE_IN == "attn":
                     ops.decode_attention_split(self.qkv, c.k[li], c.v[li], ll.cos, ll.sin, c.key_valid, B, ll.heads, 0, self.partials,
                                                past_dev=self.pos, per_row=self.per_row, out=self.att, arrivals=self.arrivals)
-                    self._o_proj(L)
+                    _gemv_residual(self, self.att, L, "o")
                 else:
                     ops.decode_attention_split(self.qkv, c.k[li], c.v[li], ll.cos, ll.sin, c.key_valid, B, ll.heads, 0,
                                                self.partials, past_dev=self.pos, per_row=self.per_row)
@@ -194,26 +210,10 @@ class DecodeSession:
                 ops.decode_attention(self.qkv, c.k[li], c.v[li], ll.cos, ll.sin, c.key_valid, B, ll.heads, 0, out=self.att,
                                      past_dev=self.pos)          # RoPE + KV append + attention in one launch
             if not split:
-                self._o_proj(L)
-            if wq_fused:
-                self.q_gemv_rmsnorm(self.h, L["ln2"], ll.eps, *L["wq_gu"], epilogue=ops.EPI_SWIGLU, out=self.mlp)
-            elif wq:
-                ops.rmsnorm(self.h, L["ln2"], ll.eps, out=self.x)
-                self.q_gemv(self.x, *L["wq_gu"], epilogue=ops.EPI_SWIGLU, out=self.mlp)
-            elif fused:
-                ops.gemv_rmsnorm(self.h, L["ln2"], ll.eps, L["w_gu"], epilogue=ops.EPI_SWIGLU, out=self.mlp)
-            else:
-                ops.rmsnorm(self.h, L["ln2"], ll.eps, out=self.x)
-                ops.gemv(self.x, L["w_gu"], epilogue=ops.EPI_SWIGLU, out=self.mlp)
-            if wq:
-                self.q_gemv(self.mlp, *L["wq_down"], residual=self.h, out=self.h)
-            else:
-                ops.gemv(self.mlp, L["w_down"], residual=self.h, out=self.h)
-        if fused:
-            ops.gemv_rmsnorm(self.h, ll.norm, ll.eps, ll.lm_head, out=self.logits)
-        else:
-            ops.rmsnorm(self.h, ll.norm, ll.eps, out=self.x)
-            ops.gemv(self.x, ll.lm_head, out=self.logits)
+                _gemv_residual(self, self.att, L, "o")
+            _norm_gemv(self, L["ln2"], L.get("w_gu"), L.get("wq_gu"), self.mlp, epilogue=ops.EPI_SWIGLU)
+            _gemv_residual(self, self.mlp, L, "down")
+        _norm_gemv(self, ll.norm, ll.lm_head, None, self.logits)
         # greedy (or sampled) next token straight into the input slot of the next step (the V-padding columns of the
         # lm_head buffer are excluded through the row stride)
         if self.beams is not None:
@@ -251,12 +251,6 @@ class DecodeSession:
         if self.lp_n is None:
             raise ValueError("record_token() needs DecodeSession(..., logprobs=n)")
         self._record(0)
-
-    def _o_proj(self, L):
-        if self.wq:
-            self.q_gemv(self.att, *L["wq_o"], residual=self.h, out=self.h)
-        else:
-            ops.gemv(self.att, L["w_o"], residual=self.h, out=self.h)
 
     def _ensure_kv_table(self):
         """The per-layer K / V pointer table of the reorder (raw pointers: rebuilt when the cache's storage moved)."""

@@ -1814,6 +1814,43 @@ SPEC_SPLITS = 4          # VLY_SPEC_SPLITS
 SPEC_PARTIAL = 132       # VLY_SPEC_PARTIAL
 
 
+def _spec_geometry(name: str, B: int, S: int, heads: int, qkv: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor,
+                   past_len: Optional[int] = None) -> int:
+    """The shapes of a verify step's rows and caches, for the single-sequence wrappers (``past_len``: the host-side position, which
+    must leave room for the S rows) and the per-sequence ones (positions on the device: None) -> ctx_max."""
+    if not 1 <= int(S) <= SPEC_MAX_QUERIES:
+        raise ValueError(f"{name}: S must be in [1, {SPEC_MAX_QUERIES}], got {S}")
+    if past_len is None and (B < 1 or heads < 1):
+        raise ValueError(f"{name}: B >= 1 and heads >= 1 expected, got {B}, {heads}")
+    if past_len is not None and (B < 1 or heads < 1 or past_len < 0):
+        raise ValueError(f"{name}: B >= 1, heads >= 1 and past_len >= 0 expected, got {B}, {heads}, {past_len}")
+    if kcache.dim() != 4 or tuple(kcache.shape[:2]) != (B, heads) or kcache.shape[3] != 128 or vcache.shape != kcache.shape:
+        raise ValueError(f"{name}: kcache / vcache [{B}, {heads}, ctx_max, 128] expected, got {tuple(kcache.shape)} / "
+                         f"{tuple(vcache.shape)}")
+    ctx_max = kcache.shape[2]
+    if past_len is not None and past_len + S > ctx_max:
+        raise ValueError(f"{name}: past_len + S = {past_len + S} exceeds the cache's {ctx_max} positions")
+    if tuple(qkv.shape) != (B * S, 3 * heads * 128):
+        raise ValueError(f"{name}: qkv [{B * S}, {3 * heads * 128}] expected, got {tuple(qkv.shape)}")
+    return ctx_max
+
+
+def _spec_attention_tensors(name: str, B: int, S: int, heads: int, qkv, kcache, vcache, scratch, key_valid, out) -> torch.Tensor:
+    """What the two split-attention wrappers check alike behind their own refusals: out's shape, then every tensor's device, dtype
+    and layout -> out (allocated when None)."""
+    if out is not None and tuple(out.shape) != (B * S, heads * 128):
+        raise ValueError(f"{name}: out [{B * S}, {heads * 128}] expected, got {tuple(out.shape)}")
+    for t, dtype, what in ((qkv, runtime.HALF, "qkv"), (kcache, runtime.HALF, "kcache"), (vcache, runtime.HALF, "vcache"),
+                           (scratch[0], torch.float32, "partials"), (scratch[1], torch.int32, "arrivals")):
+        _chk(t, dtype, what)
+    if key_valid is not None:
+        _chk(key_valid, torch.uint8, "key_valid", contiguous=False)
+    if out is None:
+        out = torch.empty((B * S, heads * 128), dtype=runtime.HALF, device=qkv.device)
+    _chk(out, runtime.HALF, "out")
+    return out
+
+
 def spec_scratch(B: int, S: int, heads: int, device):
     """``(partials, arrivals)`` of ``spec_attention`` for B sequences of S queries: fp32 scratch and the zeroed tickets."""
     return (torch.empty((B * heads * S * SPEC_SPLITS * SPEC_PARTIAL,), dtype=torch.float32, device=device),
@@ -1826,18 +1863,7 @@ def spec_attention(qkv: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor
     (sequence, head) over four workgroups — ``llama_attention``'s arguments (qkv holds the ROTATED q, the caches already
     hold positions past .. past + S - 1: what ``rope_kv`` leaves) plus ``scratch`` from ``spec_scratch``.  The row of the
     query at position P does not depend on S or on its index in the launch, bit for bit."""
-    if not 1 <= int(S) <= SPEC_MAX_QUERIES:
-        raise ValueError(f"spec_attention: S must be in [1, {SPEC_MAX_QUERIES}], got {S}")
-    if B < 1 or heads < 1 or past_len < 0:
-        raise ValueError(f"spec_attention: B >= 1, heads >= 1 and past_len >= 0 expected, got {B}, {heads}, {past_len}")
-    if kcache.dim() != 4 or tuple(kcache.shape[:2]) != (B, heads) or kcache.shape[3] != 128 or vcache.shape != kcache.shape:
-        raise ValueError(f"spec_attention: kcache / vcache [{B}, {heads}, ctx_max, 128] expected, got {tuple(kcache.shape)} / "
-                         f"{tuple(vcache.shape)}")
-    ctx_max = kcache.shape[2]
-    if past_len + S > ctx_max:
-        raise ValueError(f"spec_attention: past_len + S = {past_len + S} exceeds the cache's {ctx_max} positions")
-    if tuple(qkv.shape) != (B * S, 3 * heads * 128):
-        raise ValueError(f"spec_attention: qkv [{B * S}, {3 * heads * 128}] expected, got {tuple(qkv.shape)}")
+    ctx_max = _spec_geometry("spec_attention", B, S, heads, qkv, kcache, vcache, past_len)
     partials, arrivals = scratch
     if partials.numel() < B * heads * S * SPEC_SPLITS * SPEC_PARTIAL or arrivals.numel() < B * heads:
         raise ValueError("spec_attention: scratch too small for this launch (ops.spec_scratch(B, S, heads, device))")
@@ -1848,21 +1874,10 @@ def spec_attention(qkv: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor
         if past_dev is not None and key_valid.shape[1] < ctx_max:
             raise ValueError("spec_attention: with a device-side position key_valid must span the cache's ctx_max columns")
         kv_stride = key_valid.stride(0)
-    if out is not None and tuple(out.shape) != (B * S, heads * 128):
-        raise ValueError(f"spec_attention: out [{B * S}, {heads * 128}] expected, got {tuple(out.shape)}")
-    from . import lib_spec
-    _chk(qkv, runtime.HALF, "qkv")
-    _chk(kcache, runtime.HALF, "kcache")
-    _chk(vcache, runtime.HALF, "vcache")
-    _chk(partials, torch.float32, "partials")
-    _chk(arrivals, torch.int32, "arrivals")
-    if key_valid is not None:
-        _chk(key_valid, torch.uint8, "key_valid", contiguous=False)
+    out = _spec_attention_tensors("spec_attention", B, S, heads, qkv, kcache, vcache, scratch, key_valid, out)
     if past_dev is not None:
         _chk(past_dev, torch.int32, "past_dev")
-    if out is None:
-        out = torch.empty((B * S, heads * 128), dtype=runtime.HALF, device=qkv.device)
-    _chk(out, runtime.HALF, "out")
+    from . import lib_spec
     rc = lib_spec.load().vly_spec_attention(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), _ptr(key_valid), kv_stride,
                                                  out.data_ptr(), B, int(S), heads, int(past_len), _ptr(past_dev), ctx_max,
                                                  partials.data_ptr(), arrivals.data_ptr(), _wq_dtype(), _stream())
@@ -1960,19 +1975,6 @@ def _rows_live(name: str, live, B: int) -> None:
                          f"{tuple(getattr(live, 'shape', ()))}")
 
 
-def _rows_geometry(name: str, B: int, S: int, heads: int, qkv: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor) -> int:
-    if not 1 <= int(S) <= SPEC_MAX_QUERIES:
-        raise ValueError(f"{name}: S must be in [1, {SPEC_MAX_QUERIES}], got {S}")
-    if B < 1 or heads < 1:
-        raise ValueError(f"{name}: B >= 1 and heads >= 1 expected, got {B}, {heads}")
-    if kcache.dim() != 4 or tuple(kcache.shape[:2]) != (B, heads) or kcache.shape[3] != 128 or vcache.shape != kcache.shape:
-        raise ValueError(f"{name}: kcache / vcache [{B}, {heads}, ctx_max, 128] expected, got {tuple(kcache.shape)} / "
-                         f"{tuple(vcache.shape)}")
-    if tuple(qkv.shape) != (B * S, 3 * heads * 128):
-        raise ValueError(f"{name}: qkv [{B * S}, {3 * heads * 128}] expected, got {tuple(qkv.shape)}")
-    return kcache.shape[2]
-
-
 def spec_rows_scratch(B: int, S: int, heads: int, device):
     """``(partials, arrivals)`` of ``spec_rows_attention`` for B sequences of S queries (``spec_scratch``'s layout)."""
     return spec_scratch(B, S, heads, device)
@@ -1983,7 +1985,7 @@ def spec_rows_rope_kv(qkv: torch.Tensor, kcache: torch.Tensor, vcache: torch.Ten
     """vly_spec_rows_rope_kv: ``rope_kv`` of B sequences of S rows, sequence b at position pos[b] (clamped to [0, ctx_max - 1]):
     q of qkv [B * S, 3 * heads * 128] rotated in place, rotated k and v to cache rows pos[b] + j.  A live row's bits are
     ``rope_kv(B=1, S, past=pos[b])``'s; a row behind the cache's end is dead (nothing written, q left as it is)."""
-    ctx_max = _rows_geometry("spec_rows_rope_kv", B, S, heads, qkv, kcache, vcache)
+    ctx_max = _spec_geometry("spec_rows_rope_kv", B, S, heads, qkv, kcache, vcache)
     _rows_pos("spec_rows_rope_kv", pos, B)
     for t, name in ((cos, "cos"), (sin, "sin")):
         if t.dim() != 2 or t.shape[0] < ctx_max or t.shape[1] != 64 or t.dtype != torch.float32 or not t.is_contiguous():
@@ -2005,7 +2007,7 @@ def spec_rows_attention(qkv: torch.Tensor, kcache: torch.Tensor, vcache: torch.T
     """vly_spec_rows_attention: ``spec_attention`` with one position per sequence (pos int32 [B]).  The row of the query at
     absolute position P is bit for bit the row ``spec_attention`` writes for that position: it does not depend on S, B, the
     query's index or the other sequences' positions."""
-    ctx_max = _rows_geometry("spec_rows_attention", B, S, heads, qkv, kcache, vcache)
+    ctx_max = _spec_geometry("spec_rows_attention", B, S, heads, qkv, kcache, vcache)
     _rows_pos("spec_rows_attention", pos, B)
     partials, arrivals = scratch
     if partials.numel() < B * heads * S * SPEC_SPLITS * SPEC_PARTIAL or arrivals.numel() < B * heads:
@@ -2016,20 +2018,9 @@ def spec_rows_attention(qkv: torch.Tensor, kcache: torch.Tensor, vcache: torch.T
             raise ValueError(f"spec_rows_attention: key_valid [{B}, >= {ctx_max}] (the cache's ctx_max columns) expected, got "
                              f"{tuple(key_valid.shape)}")
         kv_stride = key_valid.stride(0)
-    if out is not None and tuple(out.shape) != (B * S, heads * 128):
-        raise ValueError(f"spec_rows_attention: out [{B * S}, {heads * 128}] expected, got {tuple(out.shape)}")
-    from . import lib_spec_rows
-    _chk(qkv, runtime.HALF, "qkv")
-    _chk(kcache, runtime.HALF, "kcache")
-    _chk(vcache, runtime.HALF, "vcache")
-    _chk(partials, torch.float32, "partials")
-    _chk(arrivals, torch.int32, "arrivals")
+    out = _spec_attention_tensors("spec_rows_attention", B, S, heads, qkv, kcache, vcache, scratch, key_valid, out)
     _chk(pos, torch.int32, "pos")
-    if key_valid is not None:
-        _chk(key_valid, torch.uint8, "key_valid", contiguous=False)
-    if out is None:
-        out = torch.empty((B * S, heads * 128), dtype=runtime.HALF, device=qkv.device)
-    _chk(out, runtime.HALF, "out")
+    from . import lib_spec_rows
     rc = lib_spec_rows.load().vly_spec_rows_attention(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), _ptr(key_valid), kv_stride,
                                                       out.data_ptr(), B, int(S), heads, pos.data_ptr(), ctx_max, partials.data_ptr(),
                                                       arrivals.data_ptr(), _wq_dtype(), _stream())
