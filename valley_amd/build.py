@@ -29,6 +29,7 @@ LIB_SCORE = os.path.join(LIBDIR, "libvalley_hip_score.so")                 # tok
 LIB_SPEC = os.path.join(LIBDIR, "libvalley_hip_spec.so")                   # prompt-lookup speculation: attention, draft, acceptance
 LIB_SPEC_SAMPLE = os.path.join(LIBDIR, "libvalley_hip_spec_sample.so")     # the verify step's draw counters under seeded sampling
 LIB_SPEC_ROWS = os.path.join(LIBDIR, "libvalley_hip_spec_rows.so")         # the verify step of several sequences, one position each
+LIB_SUFFIX = os.path.join(LIBDIR, "libvalley_hip_suffix.so")               # split attention of 1..64 new queries over a cached prefix
 # the C prologue every companion compiles (error text, launch check, the version / last-error entry points)
 COMPANION_SHARED = ["companion_capi.hpp"]
 
@@ -59,6 +60,11 @@ COMPANIONS_ROWS = (
     Companion("spec_rows", LIB_SPEC_ROWS, ("spec_rows.hip",), "valley_hip_spec_rows.h",
               ("common.hpp", "spec_attn.inc", "spec_lookup.inc")),
 )
+# conversation KV reuse: a third table, walked by the same code (the two above are what the other libraries' tests count)
+COMPANIONS_SUFFIX = (
+    Companion("suffix", LIB_SUFFIX, ("suffix.hip",), "valley_hip_suffix.h", ("common.hpp",)),
+)
+ALL_COMPANIONS = (*COMPANIONS, *COMPANIONS_ROWS, *COMPANIONS_SUFFIX)
 SOURCES = ["capi.hip", "gemm_bf16.hip", "gemm_p32.hip", "gemm_p16.hip", "gemm_streamk.hip", "norm_elementwise.hip", "attention.hip", "temporal_delta.hip", "preprocess.hip", "gemv_bf16.hip", "precise_f32.hip", "gemm_skinny.hip", "decode_step.hip", "sampling.hip"]
 
 
@@ -74,8 +80,8 @@ def hipcc() -> str:
 
 def needs_build() -> bool:
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h)
-                                                                 for h in ("valley_hip.h", *(c.header for c in (*COMPANIONS, *COMPANIONS_ROWS)))]
-    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, *(c.lib for c in (*COMPANIONS, *COMPANIONS_ROWS))):
+                                                                 for h in ("valley_hip.h", *(c.header for c in ALL_COMPANIONS))]
+    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, *(c.lib for c in ALL_COMPANIONS)):
         if not os.path.exists(lib):
             return True
         t = os.path.getmtime(lib)
@@ -87,7 +93,7 @@ def needs_build() -> bool:
 def build(force: bool = False, verbose: bool = True) -> str:
     """The two shipped libraries (bf16 and fp16 storage) and the experimental one, every stale translation unit compiled in parallel."""
     os.makedirs(LIBDIR, exist_ok=True)
-    for sub in ("f16", "exp", "exp_f16", *(c.name for c in (*COMPANIONS, *COMPANIONS_ROWS))):
+    for sub in ("f16", "exp", "exp_f16", *(c.name for c in ALL_COMPANIONS)):
         os.makedirs(os.path.join(LIBDIR, sub), exist_ok=True)
     if not force and not needs_build():
         return LIB
@@ -116,7 +122,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
             jobs.append((s, cmd))
             if s in AUDITED:
                 audits.append((s, odir, " ".join(flags) or "(default flags)"))
-    for c in (*COMPANIONS, *COMPANIONS_ROWS):
+    for c in ALL_COMPANIONS:
         cdir = os.path.join(LIBDIR, c.name)
         for s in c.sources:
             o = os.path.join(cdir, s.replace(".hip", ".o"))
@@ -166,7 +172,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
-    for c in (*COMPANIONS, *COMPANIONS_ROWS):
+    for c in ALL_COMPANIONS:
         cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", c.lib] + \
             [os.path.join(LIBDIR, c.name, s.replace(".hip", ".o")) for s in c.sources]
         if verbose:

@@ -208,16 +208,17 @@ def conv_user_turn(qs: str, n_frames: int, image_token_len: int = 256, use_im_st
 
 
 def assistant_out(model, conv, tokenizer, input_ids, image_tensor, prompt_lookup: Optional[int] = None,
-                  seed: Optional[int] = None) -> str:
+                  seed: Optional[int] = None, prefix=None) -> str:
     """run_valley_conv.py:54-92: sampled generate (T = 0.2, up to 1024 tokens, stop on '###'), strip the role prefixes,
     cut at the separator, newlines removed.  ``prompt_lookup`` / ``seed``: speculative decoding of the seeded sequence
-    (``lookup_kwargs``); with neither, ``generate`` gets exactly the reference's arguments."""
+    (``lookup_kwargs``); with neither, ``generate`` gets exactly the reference's arguments.  ``prefix``: the video's
+    valley_amd.prefix.PrefixSession (--reuse-kv) — the turn computes only what follows the dialogue its cache already holds."""
     from .video import KeywordsStoppingCriteria
     stopping = KeywordsStoppingCriteria(["###"], tokenizer, input_ids)
     with torch.inference_mode():
         output_ids = model.generate(input_ids, images=image_tensor.unsqueeze(0), do_sample=True, temperature=0.2,
                                     max_new_tokens=1024, stopping_criteria=[stopping],
-                                    **lookup_kwargs(prompt_lookup, seed, sampled=True))
+                                    **lookup_kwargs(prompt_lookup, seed, sampled=True), **({} if prefix is None else {"prefix": prefix}))
     n_in = input_ids.shape[1]
     n_diff = (input_ids != output_ids[:, :n_in]).sum().item()
     if n_diff > 0:
@@ -256,9 +257,15 @@ def conv_inference(args, read_line=input, emit=print):
     image_token_len = conv_bind_tokens(model, tokenizer)
     use_se = getattr(model.config, "mm_use_im_start_end", False)
     video_path, conv, image_tensor = "", None, None
+    session = None                                                    # --reuse-kv: one KV-cache session per opened video
+    if getattr(args, "reuse_kv", False):
+        from .prefix import PrefixSession
+        session = PrefixSession(model)
 
     def open_video(path):
         video = load_video(path).permute(1, 0, 2, 3)                  # [T,3,224,224]
+        if session is not None:
+            session.reset()                                           # another video: nothing of the old dialogue is reused
         return video.to(device), conv_templates[args.conv_mode].copy()
 
     while True:
@@ -279,7 +286,7 @@ def conv_inference(args, read_line=input, emit=print):
             conv.append_message(conv.roles[0], qs)
             input_ids = torch.as_tensor(tokenizer([conv.get_prompt()]).input_ids).to(device)
             answer = assistant_out(model, conv, tokenizer, input_ids, image_tensor, getattr(args, "prompt_lookup", None),
-                                   getattr(args, "seed", None))
+                                   getattr(args, "seed", None), **({} if session is None else {"prefix": session}))
             conv.append_message(conv.roles[1], answer)
             emit("Assistant: " + answer.strip() + "\n")
         except Exception as e:  # noqa: BLE001 - the reference prints the error as the assistant's turn and keeps going
@@ -298,6 +305,9 @@ def conv_parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
                          "answers are the ones the same --seed gives without it)")
     ap.add_argument("--seed", type=int, default=None, metavar="N",
                     help="seed of the on-device draws; with --prompt-lookup a missing seed is drawn once and printed to stderr")
+    ap.add_argument("--reuse-kv", action="store_true",
+                    help="keep the KV cache across the turns of a video's dialogue (valley_amd.prefix.PrefixSession): a turn computes "
+                         "only the tokens behind what the cache already holds; reset on 'change video'")
     return ap.parse_args(argv)
 
 

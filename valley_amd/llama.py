@@ -103,6 +103,13 @@ class HipKVCache:
         c.generation, c.growable, c.limit = 0, False, parent.ctx_max
         return c
 
+    def truncate(self, n: int) -> None:
+        """Forget the positions from ``n`` on: ``seq_len = n``.  The rows behind it stay in memory and are invisible — every kernel
+        masks keys from kv_len on, and the next forward overwrites them (valley_amd.prefix keeps a conversation's common prefix)."""
+        if not 0 <= int(n) <= self.seq_len:
+            raise ValueError(f"truncate: n must be in [0, {self.seq_len}], got {n}")
+        self.seq_len = int(n)
+
     def get_seq_length(self, layer_idx: int = 0) -> int:
         return self.seq_len
 
@@ -243,13 +250,16 @@ class HipLlama:
         return ws
 
     def forward(self, h: torch.Tensor, B: int, S: int, cache: HipKVCache, n_layers: Optional[int] = None,
-                collect: Optional[list] = None, attn: Optional[list] = None) -> torch.Tensor:
+                collect: Optional[list] = None, attn: Optional[list] = None, suffix_attention: bool = False) -> torch.Tensor:
         """h fp32 [B*S, H] (modified in place) -> final-norm hidden bf16 [B*S, H].  Appends S
         positions to ``cache``; key validity comes from cache.key_valid.  ``collect`` (a list): HF's ``output_hidden_states``
         (hf:llama/modeling_llama.py LlamaModel.forward) — receives the embeddings, every decoder layer's output (fp32
         copies of the residual stream) and, last, the final-norm output; costs one residual flush + copy per layer.
         ``attn`` (a list): HF's ``output_attentions`` — receives every layer's probabilities, fp32 [B, heads, S, kv_len]
-        (ops.attention_probs: a separate pass per layer behind the RoPE launch; the attention kernels themselves are unchanged)."""
+        (ops.attention_probs: a separate pass per layer behind the RoPE launch; the attention kernels themselves are unchanged).
+        ``suffix_attention``: in the prefill branch (S > 1, no ``attn``) with S <= ops.SUFFIX_MAX_QUERIES, the attention is
+        ops.suffix_attention — the split kernel for a short run of new tokens over a long cached prefix — where
+        ops.llama_attention runs otherwise.  Off by default: every other launch, and every caller that does not ask, is unchanged."""
         if not self.loaded:
             raise RuntimeError("Llama engine has no weights")
         past = cache.seq_len
@@ -258,14 +268,19 @@ class HipLlama:
             raise ValueError("cache batch mismatch")
         ops.sk_check_polled(self.device)                   # a stream-K hand-off failure of an earlier call surfaces here
         with runtime.stream_lock():                        # launch sequences on one stream must not interleave
-            out = self._forward_locked(h, B, S, cache, past, n_layers, collect, attn)
+            out = self._forward_locked(h, B, S, cache, past, n_layers, collect, attn, suffix_attention)
             if S > 1:
                 ops.sk_poll_async(self.device)
             return out
 
-    def _forward_locked(self, h, B, S, cache, past, n_layers, collect=None, attn=None):
+    def _forward_locked(self, h, B, S, cache, past, n_layers, collect=None, attn=None, suffix_attention=False):
         M = B * S
         ws = self._workspace(M)
+        sx = None                  # the split suffix attention's scratch, when this pass runs it
+        if suffix_attention and attn is None and 1 < S <= ops.SUFFIX_MAX_QUERIES:
+            sx = ws.get("suffix")
+            if sx is None:
+                sx = ws["suffix"] = ops.suffix_scratch(B, S, self.heads, self.device)
         kv = cache.key_valid                                # uint8 [B, ctx_max] or None (row stride = ctx_max)
         nl = self.L if n_layers is None else n_layers
         fused = M > 8            # prefill: residual adds ride on the norm kernels; decode keeps the GEMV epilogue
@@ -302,7 +317,10 @@ class HipLlama:
                 # one launch less; +0.3 % on c3)
                 ops.gemm_qkv_rope(ws["x"], W["w_qkv"], ws["qkv"], ops.RopeKV(cache.k[li], cache.v[li], self.cos, self.sin, B, S,
                                                                             self.heads, past))
-                ops.llama_attention(ws["qkv"], cache.k[li], cache.v[li], kv, B, S, self.heads, past, out=ws["att"])
+                if sx is not None:
+                    ops.suffix_attention(ws["qkv"], cache.k[li], cache.v[li], kv, B, S, self.heads, past, sx, out=ws["att"])
+                else:
+                    ops.llama_attention(ws["qkv"], cache.k[li], cache.v[li], kv, B, S, self.heads, past, out=ws["att"])
             if fused:
                 # o_proj / down_proj have fewer output tiles than the chip has CUs at prefill sizes: the tuner may
                 # answer with a split-K pair whose two bf16 partials the add+norm kernel sums

@@ -2102,3 +2102,76 @@ def spec_rows_counters(pos: torch.Tensor, k: int, ctx_max: int, out: torch.Tenso
     rc = lib_spec_rows.load().vly_spec_rows_counters(pos.data_ptr(), B, k, int(ctx_max), out.data_ptr(), _stream())
     lib_spec_rows.check(rc, "vly_spec_rows_counters")
     return out
+
+
+# ---- conversation KV reuse: split attention of a short suffix (libvalley_hip_suffix.so, include/valley_hip_suffix.h) -------------
+SUFFIX_MAX_QUERIES = 64  # VLY_SUFFIX_MAX_QUERIES
+SUFFIX_MAX_SPLITS = 16   # VLY_SUFFIX_MAX_SPLITS
+SUFFIX_PARTIAL = 132     # VLY_SUFFIX_PARTIAL
+
+
+def _suffix_scratch_words(B: int, S: int, heads: int) -> int:
+    return B * heads * S * SUFFIX_MAX_SPLITS * SUFFIX_PARTIAL + B * heads            # vly_suffix_scratch_bytes / 4
+
+
+def suffix_scratch(B: int, S: int, heads: int, device) -> torch.Tensor:
+    """The scratch of ``suffix_attention`` for B sequences of up to S queries: fp32 partials followed by the ticket counters, zeroed
+    here once (every completed launch leaves the counters at zero)."""
+    if not 1 <= int(S) <= SUFFIX_MAX_QUERIES or B < 1 or heads < 1:
+        raise ValueError(f"suffix_scratch: B >= 1, heads >= 1 and S in [1, {SUFFIX_MAX_QUERIES}] expected, got {B}, {heads}, {S}")
+    return torch.zeros((_suffix_scratch_words(B, int(S), heads),), dtype=torch.int32, device=device)
+
+
+def suffix_attention(qkv: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_valid: Optional[torch.Tensor], B: int, S: int, heads: int,
+                     past: int, scratch: torch.Tensor, past_dev: Optional[torch.Tensor] = None, out=None) -> torch.Tensor:
+    """vly_suffix_attention: ``llama_attention``'s contract (qkv holds the ROTATED q, the caches already hold the rows
+    [past, past + S)) for 1 <= S <= 64 new queries, every (sequence, head) split over the keys into workgroups of four waves
+    whose partial (max, sum, P.V) the last one to arrive merges.  ``scratch`` from ``suffix_scratch``.  Every refusal below is a
+    ValueError raised before the library is loaded."""
+    name = "suffix_attention"
+    if isinstance(S, bool) or not 1 <= int(S) <= SUFFIX_MAX_QUERIES:
+        raise ValueError(f"{name}: S must be in [1, {SUFFIX_MAX_QUERIES}], got {S}")
+    S = int(S)
+    if B < 1 or heads < 1 or past < 0:
+        raise ValueError(f"{name}: B >= 1, heads >= 1 and past >= 0 expected, got {B}, {heads}, {past}")
+    tensors = [(qkv, runtime.HALF, "qkv"), (k, runtime.HALF, "k"), (v, runtime.HALF, "v"), (scratch, torch.int32, "scratch")]
+    if key_valid is not None:
+        tensors.append((key_valid, torch.uint8, "key_valid"))
+    if past_dev is not None:
+        tensors.append((past_dev, torch.int32, "past_dev"))
+    if out is not None:
+        tensors.append((out, runtime.HALF, "out"))
+    for t, dtype, what in tensors:
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise ValueError(f"{name}: {what} must be a {dtype} tensor, got {getattr(t, 'dtype', type(t))}")
+        if not t.is_cuda or t.device != qkv.device:
+            raise ValueError(f"{name}: {what} must live on the GPU of qkv (valley_amd has no CPU compute path), got {t.device}")
+        if what != "key_valid" and not t.is_contiguous():
+            raise ValueError(f"{name}: {what} must be contiguous")
+    if k.dim() != 4 or tuple(k.shape[:2]) != (B, heads) or k.shape[3] != 128 or v.shape != k.shape:
+        raise ValueError(f"{name}: k / v [{B}, {heads}, ctx_max, 128] expected, got {tuple(k.shape)} / {tuple(v.shape)}")
+    ctx_max = k.shape[2]
+    if past + S > ctx_max:
+        raise ValueError(f"{name}: past + S = {past + S} exceeds the cache's {ctx_max} positions")
+    if tuple(qkv.shape) != (B * S, 3 * heads * 128):
+        raise ValueError(f"{name}: qkv [{B * S}, {3 * heads * 128}] expected, got {tuple(qkv.shape)}")
+    if out is not None and tuple(out.shape) != (B * S, heads * 128):
+        raise ValueError(f"{name}: out [{B * S}, {heads * 128}] expected, got {tuple(out.shape)}")
+    if scratch.dim() != 1 or scratch.numel() < _suffix_scratch_words(B, S, heads):
+        raise ValueError(f"{name}: scratch too small for this launch (ops.suffix_scratch(B, S, heads, device))")
+    if past_dev is not None and past_dev.numel() < 1:
+        raise ValueError(f"{name}: past_dev must hold one int32")
+    kv_stride = 0
+    if key_valid is not None:
+        if key_valid.dim() != 2 or key_valid.shape[0] != B or key_valid.shape[1] < past + S or key_valid.stride(1) != 1:
+            raise ValueError(f"{name}: key_valid [{B}, >= {past + S}] expected, got {tuple(key_valid.shape)}")
+        if past_dev is not None and key_valid.shape[1] < ctx_max:
+            raise ValueError(f"{name}: with a device-side position key_valid must span the cache's {ctx_max} columns")
+        kv_stride = key_valid.stride(0)
+    if out is None:
+        out = torch.empty((B * S, heads * 128), dtype=runtime.HALF, device=qkv.device)
+    from . import lib_suffix
+    rc = lib_suffix.load().vly_suffix_attention(qkv.data_ptr(), k.data_ptr(), v.data_ptr(), _ptr(key_valid), kv_stride, out.data_ptr(),
+                                                B, S, heads, int(past), _ptr(past_dev), ctx_max, _wq_dtype(), scratch.data_ptr(), _stream())
+    lib_suffix.check(rc, "vly_suffix_attention")
+    return out

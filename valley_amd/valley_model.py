@@ -352,9 +352,11 @@ class ValleyLlamaModel:
 
     def forward(self, input_ids=None, attention_mask=None, past_key_values=None, inputs_embeds=None, use_cache=None,
                 output_attentions=None, output_hidden_states=None, images=None, return_dict=None,
-                visual_tokens: Optional[torch.Tensor] = None, frames_per_clip: Optional[Sequence[int]] = None):
+                visual_tokens: Optional[torch.Tensor] = None, frames_per_clip: Optional[Sequence[int]] = None,
+                suffix_attention: bool = False):
         """valley_model.py:135-254.  ``visual_tokens``/``frames_per_clip`` let a caller that already
-        encoded (e.g. the frame-DP path, valley_amd/parallel.py) skip the tower."""
+        encoded (e.g. the frame-DP path, valley_amd/parallel.py) skip the tower.  ``suffix_attention``: HipLlama.forward's
+        switch (a short run of new tokens over a filled cache on the split kernel; valley_amd.prefix sets it)."""
         if inputs_embeds is not None:
             h = inputs_embeds.to(self.device, torch.float32).reshape(-1, self.config.hidden_size).contiguous().clone()
             B, S = inputs_embeds.shape[:2]
@@ -385,7 +387,7 @@ class ValleyLlamaModel:
         # valley_model.py:281,324-330 -> HF LlamaModel's all_self_attns: per layer [B, heads, S, kv_len] in the model dtype (HF's
         # eager attention returns the fp32 softmax cast to the query dtype); a separate pass per layer (ops.attention_probs)
         attns = [] if output_attentions else None
-        x = self.llama.forward(h, B, S, cache, collect=states, attn=attns)
+        x = self.llama.forward(h, B, S, cache, collect=states, attn=attns, **({"suffix_attention": True} if suffix_attention else {}))
         return BaseModelOutputWithPast(last_hidden_state=x.view(B, S, -1), past_key_values=cache if use_cache else None,
                                        hidden_states=None if states is None else tuple(t.view(B, S, -1) for t in states),
                                        attentions=None if attns is None else tuple(a.to(self.wdtype) for a in attns))
@@ -645,7 +647,7 @@ class ValleyLlamaForCausalLM:
                  seed=None, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False,
                  num_return_sequences: int = 1, return_dict_in_generate: bool = False, repetition_penalty=None,
                  no_repeat_ngram_size=None, min_length=None, min_new_tokens=None, output_logprobs: bool = False,
-                 top_logprobs: int = 0, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, **kw):
+                 top_logprobs: int = 0, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, prefix=None, **kw):
         """Prefill + per-token KV decode (the loop of serve/model_worker.py:371-394; the reference's CLI
         path reaches the same through HF ``generate``, valley_model.py:432).  Greedy when not sampling or
         temperature < 1e-4, else temperature softmax + multinomial.  Decode steps run through a
@@ -685,7 +687,21 @@ class ValleyLlamaForCausalLM:
         (one int, or a list of one): row j of the verify step then draws with the counter of the position it would occupy,
         the leading drafts that equal those draws are accepted, and the sequence is token for token the one the same
         seeded call returns without the two arguments.  ``do_sample=True`` without a seed is refused: there is no sequence
-        to agree with."""
+        to agree with.
+
+        ``prefix`` (a valley_amd.prefix.PrefixSession): the KV cache of this call is the session's.  Only the tokens behind
+        the longest common prefix of ``input_ids`` and what the session holds are computed (nothing is reused when the frames
+        changed or a visual placeholder lies behind the prefix); afterwards the session holds the returned sequence.  The
+        tokens are the ones the same call returns without it, up to the rounding of a prefill cut in two.  One prompt row, no
+        beams, no padding mask, a 16-bit engine — anything else is refused before a launch.  Everything else the one-row call
+        takes (sampling, the processors, ``output_logprobs``, ``prompt_lookup_num_tokens``, every ``use_graph``, the int8 and
+        int4 engines) works unchanged: the loops below are the same, only their cache and first forward come from the session."""
+        if prefix is not None:
+            if num_beams is not None and not isinstance(num_beams, bool) and int(num_beams) > 1:
+                raise ValueError("prefix= is not supported with num_beams > 1 (the beams' rows are not a session's one row)")
+            prefix.refuse(input_ids, attention_mask, self.model.precision, "generate(prefix=)")
+            if prefix.model is not self:
+                raise ValueError("generate(prefix=): the session belongs to another model")
         spec = self._spec_args(prompt_lookup_num_tokens, max_matching_ngram_size, input_ids, do_sample, num_beams, repetition_penalty,
                                no_repeat_ngram_size, min_length, min_new_tokens, output_logprobs or top_logprobs, use_graph, seed)
         proc = (repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens)
@@ -714,12 +730,12 @@ class ValleyLlamaForCausalLM:
             raise ValueError("num_return_sequences > 1 needs num_beams > 1 (sampling several sequences per prompt is not supported)")
         if spec is not None:
             seq, speculation = self._generate_spec(input_ids, images, attention_mask, max_new_tokens, stopping_criteria, eos_token_id,
-                                                   bool(use_graph), spec, do_sample, temperature, top_k, top_p)
+                                                   bool(use_graph), spec, do_sample, temperature, top_k, top_p, prefix=prefix)
             return SimpleNamespace(sequences=seq, sequences_scores=None, speculation=speculation) if return_dict_in_generate else seq
         lp_out = {} if output_logprobs else None
         seq = self._generate(input_ids, images, attention_mask, max_new_tokens, do_sample, temperature, stopping_criteria,
                              eos_token_id, use_graph, top_k, top_p, seed, proc=proc, logprobs=top_logprobs if output_logprobs else None,
-                             lp_out=lp_out, **kw)
+                             lp_out=lp_out, prefix=prefix, **kw)
         if not return_dict_in_generate:
             return seq
         return SimpleNamespace(sequences=seq, sequences_scores=None, **(lp_out or {}))
@@ -765,7 +781,7 @@ class ValleyLlamaForCausalLM:
         return k, max_ngram, seed
 
     def _generate_spec(self, input_ids, images, attention_mask, max_new_tokens, stopping_criteria, eos_token_id, use_graph, spec,
-                       do_sample=False, temperature=1.0, top_k=None, top_p=None):
+                       do_sample=False, temperature=1.0, top_k=None, top_p=None, prefix=None):
         """Generation of one row through SpecDecodeSession: the tokens a step emits are appended ONE at a time, the
         EOS test and every stopping criterion see the sequence up to that token as in ``_generate``'s loop, and whatever a
         step emitted behind the stop or behind ``max_new_tokens`` is dropped.  When the cache has fewer than k + 1 positions
@@ -786,8 +802,7 @@ class ValleyLlamaForCausalLM:
         input_ids = input_ids.to(self.device)
         S = input_ids.shape[1]
         ctx = min(getattr(self.config, "max_position_embeddings", 2048), S + max_new_tokens)
-        cache = self.model.llama.new_cache(1, max(ctx, S + 1))
-        out = self.forward(input_ids=input_ids, images=images, attention_mask=attention_mask, past_key_values=cache, use_cache=True)
+        cache, out = self._prefill(prefix, input_ids, images, attention_mask, 1, S, ctx, max_new_tokens)
         eos = None
         if eos_token_id is not None:
             eos = [int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id]
@@ -848,7 +863,20 @@ class ValleyLlamaForCausalLM:
         seq = torch.cat([input_ids, torch.tensor([new], dtype=input_ids.dtype, device=self.device)], dim=1)
         speculation = sess.speculation() if sess is not None else {"steps": 0, "drafted": 0, "accepted": 0}
         speculation["steps"] += plain_steps                  # decode steps of either kind: steps + accepted = tokens they emitted
+        if prefix is not None:
+            prefix.settle(seq)
         return seq, speculation
+
+    def _prefill(self, prefix, input_ids, images, attention_mask, B, S, ctx, max_new_tokens):
+        """The cache of a generation and the forward that fills it: a new cache and the whole prompt, or — with a
+        PrefixSession — the session's cache, the tokens behind its common prefix, and room for the new tokens."""
+        if prefix is None:
+            cache = self.model.llama.new_cache(B, max(ctx, S + 1))
+            return cache, self.forward(input_ids=input_ids, images=images, attention_mask=attention_mask, past_key_values=cache,
+                                       use_cache=True)
+        out = prefix.forward(input_ids, images)
+        prefix.reserve(S + max_new_tokens)
+        return prefix.cache, out
 
     @staticmethod
     def _processor_table(proc, S: int, eos_ids, device) -> Optional[torch.Tensor]:
@@ -865,13 +893,11 @@ class ValleyLlamaForCausalLM:
         return table.to(device)
 
     def _generate(self, input_ids, images, attention_mask, max_new_tokens, do_sample, temperature, stopping_criteria, eos_token_id,
-                  use_graph, top_k, top_p, seed, proc=None, logprobs=None, lp_out=None, **kw):
+                  use_graph, top_k, top_p, seed, proc=None, logprobs=None, lp_out=None, prefix=None, **kw):
         input_ids = input_ids.to(self.device)
         B, S = input_ids.shape
         ctx = min(getattr(self.config, "max_position_embeddings", 2048), S + max_new_tokens)
-        cache = self.model.llama.new_cache(B, max(ctx, S + 1))
-        out = self.forward(input_ids=input_ids, images=images, attention_mask=attention_mask, past_key_values=cache,
-                           use_cache=True)
+        cache, out = self._prefill(prefix, input_ids, images, attention_mask, B, S, ctx, max_new_tokens)
         greedy = not (do_sample and temperature >= ops.GREEDY_T)
         sample = None                                        # per-row parameters of the on-device draw
         if not greedy and (top_k is not None or top_p is not None or seed is not None):
@@ -996,6 +1022,8 @@ class ValleyLlamaForCausalLM:
             if logprobs:
                 lp_out["top_tokens"] = torch.where(done[:, :, None], torch.full_like(parts[1], -1), parts[1])
                 lp_out["top_logprobs"] = torch.where(done[:, :, None], torch.zeros_like(parts[2]), parts[2])
+        if prefix is not None:
+            prefix.settle(seq)
         return seq
 
     def _generate_beams(self, input_ids, images, attention_mask, max_new_tokens, nb, length_penalty, early_stopping, nrs,
@@ -1199,7 +1227,7 @@ class ValleyLlamaForCausalLM:
                                                             "length_penalty", "early_stopping", "repetition_penalty",
                                                             "no_repeat_ngram_size", "min_length", "min_new_tokens",
                                                             "output_logprobs", "top_logprobs", "prompt_lookup_num_tokens",
-                                                            "max_matching_ngram_size", "seed")}
+                                                            "max_matching_ngram_size", "seed", "prefix")}
         self.last_generation = None
         if gk.get("output_logprobs"):                        # the log-probabilities of the answer: kept on ``last_generation``
             self.last_generation = self.generate(input_ids=input_ids, images=images, stopping_criteria=[stopping],
