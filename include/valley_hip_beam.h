@@ -36,7 +36,9 @@ size_t vly_beam_scratch_bytes(int B, int nb, int K);
  *   acc[r, t] = log_softmax(logits[r, :V])[t] + running[r] in fp32, with lse = m + log(sum exp(x - m)) over the row's
  *   non-NaN logits, and acc = (x - lse) + running[r];
  *   per prompt, the K largest acc over its nb * V values, ties broken by the lower flat index j * V + t.  NaN logits
- *   are never selected while K others exist; -inf is allowed.
+ *   are never selected while K others exist; -inf is allowed.  A NaN acc ranks below -inf: a prompt with fewer than K
+ *   non-NaN values fills the rest of its K with NaN entries in flat-index order, their score a NaN (bits 0xffffffff).
+ *   -0 and +0 are one value (a tie, reported as +0).
  * logits fp32 [R, ld] (ld >= V >= K), running fp32 [R], eos int32 [n_eos] (NULL when n_eos == 0).
  * Outputs [B * K]: score fp32, token int32, beam int32 (the ABSOLUTE parent row b * nb + j), hit uint8 (token in eos).
  * One 1024-thread workgroup per row finds the row's top K (radix descent over an order-preserving key); the last
@@ -54,7 +56,8 @@ int vly_beam_select(const float *score, const int32_t *token, const int32_t *bea
 /* In place, for every layer l < L and both caches: row r <- row parent[r] over positions [lo, hi) of the
  * [R, heads, ctx_max, 128] caches whose base pointers are table[l][0] (K) and table[l][1] (V) (int64 [L, 2], device).
  * hi = (pos_dev ? *pos_dev : 0) + hi_add, clamped to ctx_max, read on the device.  elem_bytes is 2 or 4; 16-byte
- * aligned bases.  Rows with parent[r] == r are neither read (as destinations) nor written.  Any parent map is correct
+ * aligned bases.  Rows with parent[r] == r are neither read (as destinations) nor written, and a row whose parent lies
+ * outside [0, R) (-1, R, ...) is left alone in the same way.  Any parent map is correct
  * (swaps, cycles, many-to-one): one workgroup owns a (layer, K | V, head) slab of every row and stages the source rows
  * of a run of positions in LDS before it writes any of them.  Copies are 16-byte vectors: bit-exact.
  * R * 128 * elem_bytes <= 32768 (R <= 128 for 2-byte, 64 for 4-byte elements). */

@@ -33,7 +33,8 @@ const char *vly_logits_last_error(void);
  *   hist int32 [R, hist_ld]: row r's token ids, positions [0, len); the whole input_ids row of HF (prompt, left padding
  *     and placeholder ids included, then every generated token).
  *   len = (len_dev ? len_dev[len_per_row ? r : 0] : 0) + len_add, clamped to hist_ld: the row's length HF's cur_len.
- *   tok int32 [R] or NULL: first hist[r, len - 1] = tok[r] (the token fed to this step is appended on the device).
+ *   tok int32 [R] or NULL: first hist[r, len - 1] = tok[r] (the token fed to this step is appended on the device); after
+ *     the clamp, so a clamped row appends at hist_ld - 1, and a row with len < 1 appends nothing.
  * In order, for each row:
  *   log_softmax != 0: x <- x - lse, lse = m + log(sum exp(x - m)) over the row's non-NaN values (0 when m is not finite),
  *     the same routine and reduction order as vly_beam_candidates (beam search's processors see log-probabilities);
@@ -42,7 +43,9 @@ const char *vly_logits_last_error(void);
  *   n > 0 and len >= n: every window [i, i + n) of hist[r, :len] whose first n - 1 ids equal the last n - 1 bans its
  *     last id (-inf);
  *   len < m: every EOS id of eos int32 [n_eos] in [0, V) gets -inf.
- * Ids outside [0, V) are skipped.  A row with p == 1, n == 0, len >= m and log_softmax == 0 is not written. */
+ * Ids outside [0, V) are skipped: they are not penalised, not banned as a window's last id and not masked as EOS ids, but
+ * inside a window's first n - 1 ids they compare like any other id.  A row with p == 1, n == 0, len >= m and
+ * log_softmax == 0 is not written. */
 int vly_logits_process(float *logits, int ld, int V, int R, const int32_t *params, int32_t *hist, int hist_ld,
                        const int32_t *len_dev, int len_per_row, int len_add, const int32_t *tok, const int32_t *eos, int n_eos,
                        int log_softmax, void *stream);
@@ -60,8 +63,9 @@ size_t vly_logits_beam_scratch_bytes(int B, int nb, int K);
 
 /* vly_beam_candidates over scores the caller has processed (vly_logits_process with log_softmax = 1):
  *   acc[r, t] = scores[r, t] + running[r] in fp32, no log-softmax; per prompt the K largest over its nb * V values, ties
- *   to the lower flat index, best first.  Arguments, outputs and limits as vly_beam_candidates'.  The same row top-K and
- *   merge (one source): for a row the processors left alone the outputs equal vly_beam_candidates' on the raw logits. */
+ *   to the lower flat index, best first.  Arguments, outputs, limits and the NaN / signed-zero rules as
+ *   vly_beam_candidates'.  The same row top-K and merge (one source): for a row the processors left alone the outputs
+ *   equal vly_beam_candidates' on the raw logits. */
 int vly_logits_beam_candidates(const float *scores, int ld, int V, int B, int nb, const float *running, int K,
                                const int32_t *eos, int n_eos, void *scratch, float *score, int32_t *token, int32_t *beam,
                                uint8_t *hit, void *stream);
