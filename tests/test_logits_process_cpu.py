@@ -75,13 +75,13 @@ def test_ops_logits_wrappers_reject_cpu_tensors():
 
 
 def test_generate_rejects_bad_processor_arguments_before_any_work():
-    from valley_amd.valley_model import ValleyLlamaForCausalLM
+    from valley_amd.generation import processor_table
     with pytest.raises(ValueError, match="penalty"):
-        ValleyLlamaForCausalLM._processor_table((0.0, None, None, None), 4, [7], "cpu")
-    assert ValleyLlamaForCausalLM._processor_table((None, None, None, None), 4, [7], "cpu") is None
-    assert ValleyLlamaForCausalLM._processor_table((1.0, 0, 3, 0), 4, [7], "cpu") is None           # nothing would act
-    assert ValleyLlamaForCausalLM._processor_table((None, None, 9, 2), 4, None, "cpu") is None      # no EOS: no min length
-    t = ValleyLlamaForCausalLM._processor_table((1.3, 2, None, 5), 4, [7], "cpu")
+        processor_table((0.0, None, None, None), 4, [7], "cpu")
+    assert processor_table((None, None, None, None), 4, [7], "cpu") is None
+    assert processor_table((1.0, 0, 3, 0), 4, [7], "cpu") is None           # nothing would act
+    assert processor_table((None, None, 9, 2), 4, None, "cpu") is None      # no EOS: no min length
+    t = processor_table((1.3, 2, None, 5), 4, [7], "cpu")
     assert t[0, 1].item() == 2 and t[0, 2].item() == 9
 
 

@@ -60,14 +60,15 @@ def test_seeded_sampling_passes_the_refusal_and_unseeded_does_not(monkeypatch):
         reached.append((a, kw))
         raise RuntimeError("first launch")
 
-    monkeypatch.setattr(m, "_generate_spec", fake_spec, raising=False)
+    from valley_amd import generation
+    monkeypatch.setattr(generation, "_generate_spec", fake_spec)
     for seed in (1, [1], (7,), 0, (1 << 64) - 1):
         with pytest.raises(RuntimeError, match="first launch"):  # (fails where the call is still refused: ValueError, do_sample)
             m.generate(ids, prompt_lookup_num_tokens=3, do_sample=True, seed=seed)
     assert len(reached) == 5
     # the spec tuple carries the one row's seed, the sampling parameters follow it
-    a = reached[1][0]
-    assert a[-5] == (3, 2, 1) and a[-4] is True
+    kw = reached[1][1]
+    assert kw["spec"] == (3, 2, 1) and kw["do_sample"] is True
     with pytest.raises(RuntimeError, match="first launch"):      # a seed does not get in the way of a greedy call
         m.generate(ids, prompt_lookup_num_tokens=3, seed=4)
     del reached[:]

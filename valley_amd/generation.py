@@ -1,0 +1,369 @@
+"""What ``ValleyLlamaForCausalLM.generate`` does behind its argument checks: the host loops over the decode sessions — greedy / sampling,
+prompt-lookup speculation, beam search — on the pieces they and ``serving.ContinuousBatcher`` share.  decode, spec and beam are
+imported where a loop needs them (a generation loads only the companion libraries it uses); a ``prefix`` session is only handed in."""
+import torch
+
+from . import ops
+
+
+def eos_ids(eos_token_id) -> list:
+    """``eos_token_id`` (None, an int or a sequence of ints) as a list of ints, [] for None."""
+    return [] if eos_token_id is None else [int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id]
+
+
+def context_limit(config, S: int, max_new_tokens: int) -> int:
+    """Positions a generation may fill: the prompt and its new tokens, within the model's position tables."""
+    return min(getattr(config, "max_position_embeddings", 2048), S + max_new_tokens)
+
+
+def criterion_answers(criteria, seqs, seq_device, device):
+    """HF's StoppingCriteriaList, lazily: each criterion is called as ``c(seqs on seq_device, None)`` and answers per row with a tensor
+    (yielded as bool [rows] on ``device``) or for the whole batch with a python bool (yielded as it is).  ANY one firing counts: the
+    caller ORs the answers into its mask, or stops at the first that fires (then no criterion behind it is called)."""
+    for c in criteria or ():
+        r = c(seqs.to(seq_device), None)
+        yield r.to(device, torch.bool).view(-1) if isinstance(r, torch.Tensor) else bool(r)
+
+
+def finish(device, *sessions, poll: bool = True) -> None:
+    """The end of a generation: synchronise; a stream-K hand-off failure (``poll``) and every session's abort word surface here at the latest."""
+    if poll:
+        ops.sk_poll_async(device)
+    torch.cuda.current_stream().synchronize()
+    if poll:
+        ops.sk_check_polled(device)
+    for s in sessions:
+        if s is not None:
+            s.check()
+
+
+def lookup_args(k, max_ngram):
+    """``(prompt_lookup_num_tokens, max_matching_ngram_size)`` checked, with HF's default 2; (None, None) when no speculation was asked for."""
+    if k is None:
+        if max_ngram is not None:
+            raise ValueError("max_matching_ngram_size needs prompt_lookup_num_tokens")
+        return None, None
+    max_ngram = 2 if max_ngram is None else max_ngram
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= ops.SPEC_MAX_DRAFT:
+        raise ValueError(f"prompt_lookup_num_tokens must be an int in [1, {ops.SPEC_MAX_DRAFT}], got {k!r}")
+    if isinstance(max_ngram, bool) or not isinstance(max_ngram, int) or not 1 <= max_ngram <= ops.SPEC_MAX_NGRAM:
+        raise ValueError(f"max_matching_ngram_size must be an int in [1, {ops.SPEC_MAX_NGRAM}], got {max_ngram!r}")
+    return k, max_ngram
+
+
+def processor_table(proc, S: int, eos, device, rows: int = 1):
+    """HF's processors of ``generate`` as ``rows`` equal rows of ops.processor_rows (checked with HF's messages), or None when
+    none of them would act (HF adds no processor: the decode is exactly the one without them)."""
+    if proc is None or all(a is None for a in proc):
+        return None
+    rp, nr, ml, mn = proc
+    table = ops.processor_rows(rp, nr, ml, mn, prompt_len=S)
+    if not eos:
+        table[:, 2] = 0                                      # HF's minimum lengths need an EOS id
+    if bool((table.view(torch.float32)[:, 0] == 1.0).all() and (table[:, 1] == 0).all() and (table[:, 2] <= S).all()):
+        return None
+    return table.to(device).expand(rows, 4).contiguous()
+
+
+def score_raw(x, n: int, rewritten: bool):
+    """(raw logits, lse, top-n ids, top-n values) of ``x``; the raw logits are a copy when processors or a sampler will rewrite ``x``.
+    The first token is, in every caller: score_raw -> ops.logits_process -> ops.argmax (counter S) -> ops.score_record of the token."""
+    raw = torch.empty_like(x) if rewritten else None
+    _, lse, tid, tl = ops.token_logprobs(x, top=n, copy=raw)
+    return (x if raw is None else raw), lse, tid, tl
+
+
+def _prefill(model, prefix, input_ids, images, attention_mask, B, S, max_new_tokens):
+    """The cache of a generation and the forward that fills it: a new cache and the whole prompt, or — with a
+    PrefixSession — the session's cache, the tokens behind its common prefix, and room for the new tokens."""
+    if prefix is None:
+        cache = model.model.llama.new_cache(B, max(context_limit(model.config, S, max_new_tokens), S + 1))
+        return cache, model.forward(input_ids=input_ids, images=images, attention_mask=attention_mask, past_key_values=cache, use_cache=True)
+    out = prefix.forward(input_ids, images)
+    prefix.reserve(S + max_new_tokens)
+    return prefix.cache, out
+
+
+def _generate_spec(model, input_ids, images, attention_mask, max_new_tokens, stopping_criteria, eos_token_id, use_graph, spec,
+                   do_sample=False, temperature=1.0, top_k=None, top_p=None, prefix=None):
+    """Generation of one row through SpecDecodeSession: the tokens a step emits are appended ONE at a time, the EOS test and every
+    stopping criterion see the sequence up to that token as in ``_generate``'s loop, and whatever a step emitted behind the stop or
+    behind ``max_new_tokens`` is dropped.  With fewer than k + 1 cache positions left, the remaining tokens come from the one-token
+    DecodeSession; the speculative session is made (warmed up and captured, which writes k + 1 cache rows) only once a step of it
+    can run, so ``max_new_tokens <= k`` never makes one.  Greedy, or seeded sampling (``generate`` admits ``do_sample`` with a seed
+    only): both sessions hold the row's parameters and every draw is keyed by (seed, index of the drawn token)."""
+    from .decode import DecodeSession
+    from .spec import SpecDecodeSession
+    k, max_ngram, seed = spec
+    sample = None                                            # the row's parameters of the on-device draw (checked before the prefill)
+    if do_sample and temperature >= ops.GREEDY_T:
+        sample = ops.sampling_rows(float(temperature), 0 if top_k is None else top_k, 1.0 if top_p is None else top_p, [seed])
+    d = model.device
+    input_ids = input_ids.to(d)
+    S = input_ids.shape[1]
+    cache, out = _prefill(model, prefix, input_ids, images, attention_mask, 1, S, max_new_tokens)
+    eos = eos_ids(eos_token_id) or None
+    if sample is not None:
+        sample = sample.to(d)
+    last = out.logits[:, -1, :].contiguous()                 # ``_generate``'s first token: the draw's counter is the prompt's length
+    new = [int((ops.argmax(last) if sample is None else ops.argmax(last, sampling=sample, ctr_add=S))[0])]
+    sess, plain, plain_steps = None, None, 0
+
+    def stopped() -> bool:
+        """EOS, or a stopping criterion on the sequence so far: a python bool stays on the host, none is called behind the first hit"""
+        if eos is not None and new[-1] in eos:
+            return True
+        if stopping_criteria is None:
+            return False
+        seq = torch.cat([input_ids, torch.tensor([new], dtype=input_ids.dtype, device=d)], dim=1)
+        return any(bool(a.all()) if isinstance(a, torch.Tensor) else a for a in criterion_answers(stopping_criteria, seq, d, d))
+
+    done = False
+    while len(new) < max_new_tokens and not done:
+        if stopped() or cache.seq_len + 1 > cache.ctx_max:
+            break
+        if plain is None and cache.seq_len + k + 1 <= cache.ctx_max:
+            if sess is None:
+                sess = SpecDecodeSession(model.model.llama, cache, k, max_ngram, eos_ids=eos, use_graph=use_graph, sampling=sample is not None)
+                if sample is not None:
+                    sess.sample.copy_(sample.expand(k + 1, 6))
+                known = torch.cat([input_ids[0], torch.tensor(new[:-1], dtype=input_ids.dtype, device=d)])
+                sess.begin(torch.tensor(new[-1:], device=d), prompt_ids=known)
+            emitted = sess.step()
+        else:                                                # the cache's last positions: one token per step
+            if plain is None:
+                plain = DecodeSession(model.model.llama, cache, use_graph=use_graph, sampling=sample is not None)
+                if sample is not None:                       # its counters go on from the cache's position: the seed's sequence
+                    plain.sample.copy_(sample)
+                plain.begin(torch.tensor([new[-1]], device=d))
+            emitted = [int(plain.step()[0])]
+            plain_steps += 1
+        for j, t in enumerate(emitted):
+            if j and stopped():                              # (before the step's first token the loop has tested already)
+                done = True
+                break
+            new.append(t)
+            if len(new) == max_new_tokens:
+                break
+    finish(d, sess, plain)
+    seq = torch.cat([input_ids, torch.tensor([new], dtype=input_ids.dtype, device=d)], dim=1)
+    speculation = sess.speculation() if sess is not None else {"steps": 0, "drafted": 0, "accepted": 0}
+    speculation["steps"] += plain_steps                      # decode steps of either kind: steps + accepted = tokens they emitted
+    if prefix is not None:
+        prefix.settle(seq)
+    return seq, speculation
+
+
+def _generate(model, input_ids, images, attention_mask, max_new_tokens, do_sample, temperature, stopping_criteria, eos_token_id,
+              use_graph, top_k, top_p, seed, pad, proc=None, logprobs=None, prefix=None):
+    """Greedy decoding and sampling: the first token from the prefill's logits, then one ``step`` per token (the decode session's, or
+    the generic forward's) until every row has finished; a finished row emits ``pad`` (HF).  -> sequences, log-probability fields."""
+    d = model.device
+    input_ids = input_ids.to(d)
+    B, S = input_ids.shape
+    cache, out = _prefill(model, prefix, input_ids, images, attention_mask, B, S, max_new_tokens)
+    greedy = not (do_sample and temperature >= ops.GREEDY_T)
+    sample = None                                            # per-row parameters of the on-device draw
+    if not greedy and (top_k is not None or top_p is not None or seed is not None):
+        if seed is None:
+            seed = int(torch.randint(0, 1 << 62, (1,)).item())           # reproducible under torch.manual_seed
+        seeds = [(int(seed) + r) % (1 << 64) for r in range(B)] if not isinstance(seed, (list, tuple)) else list(seed)
+        if len(seeds) != B:
+            raise ValueError(f"generate: {len(seeds)} seeds for {B} rows")
+        sample = ops.sampling_rows(float(temperature), 0 if top_k is None else top_k, 1.0 if top_p is None else top_p, seeds, device=d)
+    on_device = greedy or sample is not None                 # else the host draws: torch.multinomial over the step's logits
+
+    def pick(last, ctr):                                     # ctr: index of the drawn token in the sequence
+        if on_device:
+            return (ops.argmax(last) if sample is None else ops.argmax(last, sampling=sample, ctr_add=ctr)).to(torch.long)
+        return torch.multinomial(torch.softmax(last / temperature, dim=-1), num_samples=1).view(B)
+
+    eos_list = eos_ids(eos_token_id) or None
+    eos = None if eos_list is None else torch.as_tensor(eos_list, device=d)
+    if pad is None:
+        pad = int(eos[0]) if eos is not None else 0
+    finished = torch.zeros((B,), dtype=torch.bool, device=d)
+    table = processor_table(proc, S, eos_list, d, B)
+    rewritten = table is not None or sample is not None      # the logits are rewritten in place before the token is picked
+    lp_cols, lp_done = [], []                                # per new token: its [B, 1(, n)] record; the rows already finished
+
+    def record(scored, tok):
+        col = torch.zeros((B, 1), dtype=torch.float32, device=d)
+        tabs = (torch.full((B, 1, logprobs), -1, dtype=torch.int32, device=d),
+                torch.zeros((B, 1, logprobs), dtype=torch.float32, device=d)) if logprobs else None
+        ops.score_record(*scored[:2], tok.to(torch.int32), col, None, 0, top=scored[2:] if logprobs else None, top_tables=tabs)
+        lp_cols.append((col,) + (tabs or ()))
+        lp_done.append(finished.clone())
+
+    last = out.logits[:, -1, :].contiguous()
+    scored = score_raw(last, logprobs, rewritten) if logprobs is not None else None
+    eos32 = hist = None
+    if table is not None:                                    # HF's processors over each row's whole input_ids, on the device
+        eos32 = None if eos is None else eos.to(torch.int32)
+        hist = torch.zeros((B, cache.ctx_max), dtype=torch.int32, device=d)
+        hist[:, :S] = input_ids.to(torch.int32)
+        ops.logits_process(last, table, hist, None, S, None, eos32)
+    token = pick(last, S)
+    if logprobs is not None:                                 # the first token: from the prefill's last logits
+        record(scored, token)
+    seq = torch.cat([input_ids, token[:, None]], dim=1)
+    if B > 8 or model.model.precision == "fp32":
+        use_graph = None                                     # the GEMV decode session is bf16, for <= 8 sequences
+    sess, mask = None, attention_mask
+    if use_graph is not None:
+        from .decode import DecodeSession
+        sess = DecodeSession(model.model.llama, cache, use_graph=bool(use_graph), sampling=sample is not None, processors=table is not None,
+                             processor_eos=eos_list, **({} if logprobs is None else {"logprobs": logprobs}))
+        if sample is not None:
+            sess.sample.copy_(sample)
+        if table is not None:
+            sess.proc.copy_(table)
+        sess.begin(token, prompt_ids=input_ids if table is not None else None)
+
+    def session_step(token):
+        nxt = sess.step()
+        token = nxt.to(torch.long).clone() if on_device else pick(sess.logits[:, :model.model.llama.V], None)
+        if bool(finished.any()) or not on_device:
+            token = torch.where(finished, torch.full_like(token, pad), token)
+            sess.tok.copy_(token.to(torch.int32))
+            if logprobs is not None and not on_device:
+                sess.record_token()                          # the step recorded its own argmax: the host's draw replaces it
+        if logprobs is not None:
+            lp_done.append(finished.clone())
+        return token
+
+    def forward_step(token):
+        nonlocal mask
+        if mask is not None:
+            mask = torch.cat([mask.to(d), torch.ones((B, 1), dtype=mask.dtype, device=d)], dim=1)
+        last = model.forward(input_ids=token[:, None], attention_mask=mask, past_key_values=cache, use_cache=True).logits[:, -1, :].contiguous()
+        scored = score_raw(last, logprobs, rewritten) if logprobs is not None else None
+        if table is not None:                                # the fed token joins the history at index seq_len - 1
+            ops.logits_process(last, table, hist, None, cache.seq_len, token.to(torch.int32), eos32)
+        token = torch.where(finished, torch.full_like(token, pad), pick(last, cache.seq_len))
+        if logprobs is not None:
+            record(scored, token)
+        return token
+
+    step = forward_step if sess is None else session_step
+    for _ in range(max_new_tokens - 1):
+        if eos is not None:
+            finished |= torch.isin(token, eos)
+        for a in criterion_answers(stopping_criteria, seq, d, d):
+            finished |= a if isinstance(a, torch.Tensor) else torch.full_like(finished, a)
+        if bool(finished.all()) or cache.seq_len + 1 > cache.ctx_max:
+            break
+        token = step(token)
+        seq = torch.cat([seq, token[:, None]], dim=1)
+    finish(d, sess)
+    lp_out = {}
+    if logprobs is not None:                                 # one read of the session's tables, after the loop
+        parts = [torch.cat([c[k] for c in lp_cols], dim=1) for k in range(3 if logprobs else 1)]
+        if sess is not None:                                 # columns S + 1 ..: the tokens the steps chose
+            tabs = [sess.lp_table] + list(sess.lp_top_tables or ())
+            parts = [torch.cat([p, t[:, S + 1:seq.shape[1]]], dim=1) for p, t in zip(parts, tabs)]
+        done = torch.stack(lp_done, dim=1)                   # [B, new]: the row had finished before this token (a pad)
+        lp_out["token_logprobs"] = torch.where(done, torch.zeros_like(parts[0]), parts[0])
+        if logprobs:
+            lp_out["top_tokens"] = torch.where(done[:, :, None], torch.full_like(parts[1], -1), parts[1])
+            lp_out["top_logprobs"] = torch.where(done[:, :, None], torch.zeros_like(parts[2]), parts[2])
+    if prefix is not None:
+        prefix.settle(seq)
+    return seq, lp_out
+
+
+def _generate_beams(model, input_ids, images, attention_mask, max_new_tokens, nb, length_penalty, early_stopping, nrs,
+                    stopping_criteria, eos_token_id, use_graph, pad, proc=None):
+    """Beam search (HF ``_beam_search``): the B prompts are prefilled once (images, padding mask) into rows [0, B) of a B * nb-row
+    cache, whose prompt positions the reorder kernel then copies into every beam row (key_valid likewise).  Every step picks the K
+    best continuations per prompt on the device (ops.beam_candidates), selects the running beams (ops.beam_select) and makes the KV
+    rows of the generated positions follow their parents (ops.kv_beam_reorder); the host keeps the hypotheses (valley_amd.beam) from
+    one small copy of the candidates.  Up to 8 rows the step is the decode session's (captured or eager); otherwise, or with
+    ``use_graph=None``, the generic forward followed by the same three kernels.  Stopping criteria are evaluated on the host over the
+    [B * K, cur_len + 1] candidate sequences, as HF does, and hand the hit mask to the select kernel.  With processors every beam row
+    keeps its token history on the device (following its parent, as its KV rows do); candidates: over the processed log_softmax."""
+    from .beam import BeamSearch
+    from .decode import DecodeSession
+    d = model.device
+    input_ids = input_ids.to(d)
+    B, S = input_ids.shape
+    R, ll = B * nb, model.model.llama
+    eos = eos_ids(eos_token_id)
+    max_len = context_limit(model.config, S, max_new_tokens)
+    if max_len <= S:
+        return input_ids.clone(), torch.zeros((B * nrs,), dtype=torch.float32)
+    state = BeamSearch(input_ids, nb, max_len, eos_ids=eos, pad_token_id=pad, length_penalty=length_penalty,
+                       early_stopping=early_stopping, num_return_sequences=nrs)
+    K = state.K
+    if state.K > ops.BEAM_MAX_K or nb > ops.BEAM_MAX_NB:
+        raise ValueError(f"beam search takes num_beams <= {ops.BEAM_MAX_NB} and max(2, 1 + n_eos) * num_beams <= "
+                         f"{ops.BEAM_MAX_K} (got {nb} beams, {len(eos)} EOS ids)")
+    cache = ll.new_cache(R, max_len + 1)
+    prompt = type(cache).rows_of(cache, 0, B)                # (HipKVCache, or the fp32 engine's F32KVCache)
+    out = model.forward(input_ids=input_ids, images=images, attention_mask=attention_mask, past_key_values=prompt, use_cache=True)
+    expand = torch.arange(R, dtype=torch.int32, device=d) // nb          # row b * nb + j <- prompt row b
+    kv_table = ops.kv_beam_table(cache.k, cache.v, d)
+    ops.kv_beam_reorder(kv_table, cache.k[0], expand, 0, S)
+    cache.seq_len = S
+    if prompt.key_valid is not None:
+        cache.key_valid = prompt.key_valid.index_select(0, expand.long()).contiguous()
+    eos_dev = torch.tensor(eos, dtype=torch.int32, device=d) if eos else None
+    scratch = ops.beam_scratch(B, nb, K, d)
+    running = state.initial_running().to(d)
+    first = out.logits[:, -1, :].float().repeat_interleave(nb, dim=0).contiguous()
+    table = processor_table(proc, S, eos, d, R)
+    hist = None
+    if table is not None:                                    # every beam row's history: its prompt's whole input_ids
+        hist = torch.zeros((R, cache.ctx_max), dtype=torch.int32, device=d)
+        hist[:, :S] = input_ids.to(torch.int32).repeat_interleave(nb, dim=0)
+
+    def candidates(x, length, tok):
+        """the K best continuations per prompt of the logits ``x``; with processors, HF's: over log_softmax(x), then + running"""
+        if table is None:
+            return ops.beam_candidates(x, running, B, nb, K, eos_dev, scratch)
+        ops.logits_process(x, table, hist, None, length, tok, eos_dev, log_softmax=True)
+        return ops.logits_beam_candidates(x, running, B, nb, K, eos_dev, scratch)
+
+    def finish_step(c):
+        """the host half of a step: hits (EOS, the caller's criteria), the host state; the mask goes back when a criterion added hits"""
+        seqs = state.candidates(c[0], c[1], c[2])
+        hits = eos_hits = c[3].to("cpu", torch.bool).view(-1)
+        for a in criterion_answers(stopping_criteria if host_crit else (), seqs, d, "cpu"):
+            hits = hits | (a if isinstance(a, torch.Tensor) else torch.full_like(hits, a))
+        state.advance(hits)
+        if host_crit and bool((hits & ~eos_hits).any()):
+            c[3].copy_(hits.to(torch.uint8).to(d))
+
+    cand = candidates(first, S, None)
+    host_crit = stopping_criteria is not None and len(stopping_criteria) > 0
+    if model.model.precision == "fp32" or R > 8:
+        use_graph = None                                     # the GEMV decode session: 16-bit storage, <= 8 rows
+    sess = None
+    if use_graph is not None:
+        sess = DecodeSession(ll, cache, use_graph=bool(use_graph), beams=(B, nb, S, eos, not host_crit), processors=table is not None)
+        if table is not None:
+            sess.proc.copy_(table)
+    finish_step(cand)
+    if sess is not None and not state.done:
+        ops.beam_select(*cand, B, nb, tok=sess.tok, parent=sess.parent, running=sess.running)
+        sess.begin(sess.tok.clone(), prompt_ids=hist[:, :S] if hist is not None else None)   # (nothing to reorder yet)
+    while not state.done:
+        if sess is not None:
+            sess.step()                                      # forward + candidates (+ select, reorder, pos += 1 without criteria)
+            finish_step(sess.cand)
+            if host_crit and not state.done:
+                sess.beam_tail()
+        else:
+            tok, parent, running = ops.beam_select(*cand, B, nb, running=running)
+            if cache.seq_len > S:                            # the generated positions follow their parents
+                ops.kv_beam_reorder(kv_table, cache.k[0], parent, S, cache.seq_len)
+                if hist is not None:
+                    ops.logits_history_gather(hist, parent, S, cache.seq_len)
+            if cache.seq_len + 1 > cache.ctx_max:
+                break
+            cand = candidates(model.forward(input_ids=tok.to(torch.long)[:, None], past_key_values=cache, use_cache=True).logits[:, -1, :],
+                              cache.seq_len, tok)
+            finish_step(cand)
+    finish(d, sess, poll=False)                              # (beam search has never polled the stream-K hand-off at its end: kept so)
+    seq, scores = state.result()
+    return seq.to(d), scores

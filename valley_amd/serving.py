@@ -17,6 +17,7 @@ import torch
 
 from . import ops
 from .decode import DecodeSession
+from .generation import eos_ids, lookup_args, score_raw
 from .valley_model import (DEFAULT_IM_END_TOKEN, DEFAULT_IM_START_TOKEN, DEFAULT_IMAGE_PATCH_TOKEN, DEFAULT_VI_END_TOKEN,
                            DEFAULT_VI_START_TOKEN, DEFAULT_VIDEO_FRAME_TOKEN, DEFAULT_VIDEO_TOKEN)
 
@@ -134,15 +135,8 @@ class ContinuousBatcher:
         if not 1 <= slots <= 8:
             raise ValueError("1 <= slots <= 8 (the decode step streams weights with the GEMV kernels)")
         self.spec_k = None
-        if prompt_lookup_num_tokens is None:
-            if max_matching_ngram_size is not None:
-                raise ValueError("max_matching_ngram_size needs prompt_lookup_num_tokens")
-        else:
-            k, n = prompt_lookup_num_tokens, 2 if max_matching_ngram_size is None else max_matching_ngram_size
-            if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= ops.SPEC_MAX_DRAFT:
-                raise ValueError(f"prompt_lookup_num_tokens must be an int in [1, {ops.SPEC_MAX_DRAFT}], got {k!r}")
-            if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= ops.SPEC_MAX_NGRAM:
-                raise ValueError(f"max_matching_ngram_size must be an int in [1, {ops.SPEC_MAX_NGRAM}], got {n!r}")
+        k, n = lookup_args(prompt_lookup_num_tokens, max_matching_ngram_size)
+        if k is not None:
             if slots * (k + 1) > ops.SPEC_MAX_QUERIES:
                 raise ValueError(f"speculation verifies slots x (k + 1) <= {ops.SPEC_MAX_QUERIES} rows per step: {slots} slots x "
                                  f"(k + 1 = {k + 1}) = {slots * (k + 1)} rows")
@@ -164,7 +158,7 @@ class ContinuousBatcher:
         self.cache.key_valid = torch.ones((slots, ctx_max), dtype=torch.uint8, device=self.ll.device)
         self.sampling = sampling
         self.processors = processors
-        eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id])
+        eos = eos_ids(eos_token_id)
         if self.spec_k is not None:
             self.sess = _spec.SpecRowsSession(self.ll, self.cache, self.spec_k, max_ngram=self.spec_ngram, eos_ids=eos,
                                               use_graph=use_graph, sampling=sampling)
@@ -222,9 +216,7 @@ class ContinuousBatcher:
         scored = None
         if self.logprobs is not None:                            # the raw logits: before the processors and the draw rewrite them
             last = last.float().contiguous()
-            raw = torch.empty_like(last) if (proc is not None or params is not None) else last
-            _, lse, tid, tl = ops.token_logprobs(last, top=self.logprobs, copy=None if raw is last else raw)
-            scored = (raw, lse, tid, tl)
+            scored = score_raw(last, self.logprobs, proc is not None or params is not None)
         if proc is not None:                                     # the slot's history: the prompt; the first token is processed
             self.sess.proc[slot:slot + 1].copy_(proc)
             self.sess.hist[slot, :S] = ids[0].to(torch.int32)
@@ -234,7 +226,7 @@ class ContinuousBatcher:
             tok = int(first_token)
         elif params is not None and temperature >= ops.GREEDY_T:
             tok = int(ops.argmax(last, sampling=params, ctr_add=S)[0])
-        else:
+        else:                                                    # (a greedy request: torch's argmax of the row as the forward left it)
             tok = int(last[0].argmax())
         if self.spec_k is not None:                              # the slot's history: the prompt, then the first token
             self.sess.set_sequence(slot, S, tok, prompt_ids=ids[0], sampling_row=params)
@@ -244,11 +236,10 @@ class ContinuousBatcher:
             self.sess.pos[slot:slot + 1].fill_(S)
             self.sess.tok[slot:slot + 1].fill_(tok)
         if scored is not None:                                   # the first token sits at index S of the request's sequence
-            raw, lse, tid, tl = scored
             tabs = None if not self.logprobs else tuple(t[slot:slot + 1] for t in self.sess.lp_top_tables)
-            ops.score_record(raw, lse, self.sess.tok[slot:slot + 1], self.sess.lp_table[slot:slot + 1], None, S,
-                             top=(tid, tl) if self.logprobs else None, top_tables=tabs)
-            self.first_logprobs[slot] = self._read_logprobs(self.sess.lp_table[slot:slot + 1, S:S + 1], (tid, tl))[0]
+            ops.score_record(*scored[:2], self.sess.tok[slot:slot + 1], self.sess.lp_table[slot:slot + 1], None, S,
+                             top=scored[2:] if self.logprobs else None, top_tables=tabs)
+            self.first_logprobs[slot] = self._read_logprobs(self.sess.lp_table[slot:slot + 1, S:S + 1], scored[2:])[0]
         self.live[slot], self.length[slot] = True, S
         self.last_prefill_logits = last[0]
         return slot

@@ -21,7 +21,7 @@ from typing import Dict, List, Optional, Sequence, Union
 import numpy as np
 import torch
 
-from . import ops, ops_f32, runtime
+from . import generation, ops, ops_f32, runtime
 from .llama import HipKVCache, HipLlama
 from .precise import F32KVCache, PreciseCLIPVisionTower, PreciseLlama
 from .splice import build_row_map
@@ -722,38 +722,31 @@ class ValleyLlamaForCausalLM:
                 raise ValueError("beam sampling (num_beams > 1 with do_sample=True) is not supported")
             if num_return_sequences > num_beams:
                 raise ValueError(f"num_return_sequences ({num_return_sequences}) must be <= num_beams ({num_beams})")
-            seq, scores = self._generate_beams(input_ids, images, attention_mask, max_new_tokens, int(num_beams), length_penalty,
-                                               early_stopping, int(num_return_sequences), stopping_criteria, eos_token_id,
-                                               use_graph, kw.get("pad_token_id", getattr(self.config, "pad_token_id", None)), proc)
+            seq, scores = generation._generate_beams(self, input_ids, images, attention_mask, max_new_tokens, int(num_beams), length_penalty,
+                                                     early_stopping, int(num_return_sequences), stopping_criteria, eos_token_id, use_graph,
+                                                     kw.get("pad_token_id", getattr(self.config, "pad_token_id", None)), proc)
             return SimpleNamespace(sequences=seq, sequences_scores=scores) if return_dict_in_generate else seq
         if num_return_sequences != 1:
             raise ValueError("num_return_sequences > 1 needs num_beams > 1 (sampling several sequences per prompt is not supported)")
         if spec is not None:
-            seq, speculation = self._generate_spec(input_ids, images, attention_mask, max_new_tokens, stopping_criteria, eos_token_id,
-                                                   bool(use_graph), spec, do_sample, temperature, top_k, top_p, prefix=prefix)
+            seq, speculation = generation._generate_spec(self, input_ids, images, attention_mask, max_new_tokens, stopping_criteria, eos_token_id,
+                                                         use_graph=bool(use_graph), spec=spec, do_sample=do_sample, temperature=temperature,
+                                                         top_k=top_k, top_p=top_p, prefix=prefix)
             return SimpleNamespace(sequences=seq, sequences_scores=None, speculation=speculation) if return_dict_in_generate else seq
-        lp_out = {} if output_logprobs else None
-        seq = self._generate(input_ids, images, attention_mask, max_new_tokens, do_sample, temperature, stopping_criteria,
-                             eos_token_id, use_graph, top_k, top_p, seed, proc=proc, logprobs=top_logprobs if output_logprobs else None,
-                             lp_out=lp_out, prefix=prefix, **kw)
-        if not return_dict_in_generate:
-            return seq
-        return SimpleNamespace(sequences=seq, sequences_scores=None, **(lp_out or {}))
+        seq, lp_out = generation._generate(self, input_ids, images, attention_mask, max_new_tokens, do_sample, temperature, stopping_criteria,
+                                           eos_token_id, use_graph, top_k, top_p, seed,
+                                           kw.get("pad_token_id", getattr(self.config, "pad_token_id", None)), proc=proc,
+                                           logprobs=top_logprobs if output_logprobs else None, prefix=prefix)
+        return SimpleNamespace(sequences=seq, sequences_scores=None, **lp_out) if return_dict_in_generate else seq
 
     def _spec_args(self, k, max_ngram, input_ids, do_sample, num_beams, rp, nr, ml, mn, logprobs, use_graph, seed=None):
         """``(k, max_ngram, seed)`` of a prompt-lookup generation, or None when it was not asked for; every combination the
         speculative step does not cover is refused here, before the model is touched.  ``seed`` is the one row's seed (an
         int, or a list of one) and is what admits ``do_sample=True``: the verify step checks a draft against the draws of
         plain SEEDED decoding, which only a seed pins."""
+        k, max_ngram = generation.lookup_args(k, max_ngram)
         if k is None:
-            if max_ngram is not None:
-                raise ValueError("max_matching_ngram_size needs prompt_lookup_num_tokens")
             return None
-        max_ngram = 2 if max_ngram is None else max_ngram    # HF's default
-        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= ops.SPEC_MAX_DRAFT:
-            raise ValueError(f"prompt_lookup_num_tokens must be an int in [1, {ops.SPEC_MAX_DRAFT}], got {k!r}")
-        if isinstance(max_ngram, bool) or not isinstance(max_ngram, int) or not 1 <= max_ngram <= ops.SPEC_MAX_NGRAM:
-            raise ValueError(f"max_matching_ngram_size must be an int in [1, {ops.SPEC_MAX_NGRAM}], got {max_ngram!r}")
         if input_ids.dim() != 2 or input_ids.shape[0] != 1:
             raise ValueError("prompt_lookup_num_tokens decodes one prompt row (HF's assisted decoding is batch 1 too), got "
                              f"input_ids {tuple(input_ids.shape)}")
@@ -779,361 +772,6 @@ class ValleyLlamaForCausalLM:
         from . import spec as _spec
         _spec.refuse_engine()
         return k, max_ngram, seed
-
-    def _generate_spec(self, input_ids, images, attention_mask, max_new_tokens, stopping_criteria, eos_token_id, use_graph, spec,
-                       do_sample=False, temperature=1.0, top_k=None, top_p=None, prefix=None):
-        """Generation of one row through SpecDecodeSession: the tokens a step emits are appended ONE at a time, the
-        EOS test and every stopping criterion see the sequence up to that token as in ``_generate``'s loop, and whatever a
-        step emitted behind the stop or behind ``max_new_tokens`` is dropped.  When the cache has fewer than k + 1 positions
-        left, the remaining tokens come from the one-token DecodeSession; the speculative session is made (and its step
-        warmed up and captured, which writes k + 1 cache rows from the position on) only once a step of it can run, so a
-        call with ``max_new_tokens <= k`` never makes one.
-
-        Greedy, or — ``do_sample`` with a temperature of at least ops.GREEDY_T, which ``_spec_args`` admits with a seed only —
-        seeded sampling: the first token is ``_generate``'s draw from the prefill's last logits, both sessions are made with
-        ``sampling=True`` and hold the row's parameters, and every draw is keyed by (seed, index of the drawn token), so the
-        sequence is plain seeded decoding's whichever session, and whichever row of a verify step, drew a token."""
-        from .decode import DecodeSession
-        from .spec import SpecDecodeSession
-        k, max_ngram, seed = spec
-        sample = None                                        # the row's parameters of the on-device draw (checked before the prefill)
-        if do_sample and temperature >= ops.GREEDY_T:
-            sample = ops.sampling_rows(float(temperature), 0 if top_k is None else top_k, 1.0 if top_p is None else top_p, [seed])
-        input_ids = input_ids.to(self.device)
-        S = input_ids.shape[1]
-        ctx = min(getattr(self.config, "max_position_embeddings", 2048), S + max_new_tokens)
-        cache, out = self._prefill(prefix, input_ids, images, attention_mask, 1, S, ctx, max_new_tokens)
-        eos = None
-        if eos_token_id is not None:
-            eos = [int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id]
-        if sample is None:
-            token = int(ops.argmax(out.logits[:, -1, :].contiguous())[0])
-        else:                                                # ``_generate``'s first draw: the counter is the prompt's length
-            sample = sample.to(self.device)
-            token = int(ops.argmax(out.logits[:, -1, :].contiguous(), sampling=sample, ctr_add=S)[0])
-        new = [token]
-        sess, plain, plain_steps = None, None, 0
-
-        def stopped() -> bool:
-            """``_generate``'s test before a further token: EOS, a stopping criterion on the sequence so far, the cache."""
-            if eos is not None and new[-1] in eos:
-                return True
-            if stopping_criteria is not None:
-                seq = torch.cat([input_ids, torch.tensor([new], dtype=input_ids.dtype, device=self.device)], dim=1)
-                for c in stopping_criteria:
-                    r = c(seq, None)
-                    if bool(r.to(self.device).view(-1).all()) if isinstance(r, torch.Tensor) else bool(r):
-                        return True
-            return False
-
-        done = False
-        while len(new) < max_new_tokens and not done:
-            if stopped() or cache.seq_len + 1 > cache.ctx_max:
-                break
-            if plain is None and cache.seq_len + k + 1 <= cache.ctx_max:
-                if sess is None:
-                    sess = SpecDecodeSession(self.model.llama, cache, k, max_ngram, eos_ids=eos, use_graph=use_graph,
-                                             sampling=sample is not None)
-                    if sample is not None:
-                        sess.sample.copy_(sample.expand(k + 1, 6))
-                    known = torch.cat([input_ids[0], torch.tensor(new[:-1], dtype=input_ids.dtype, device=self.device)])
-                    sess.begin(torch.tensor(new[-1:], device=self.device), prompt_ids=known)
-                emitted = sess.step()
-            else:                                            # the cache's last positions: one token per step
-                if plain is None:
-                    plain = DecodeSession(self.model.llama, cache, use_graph=use_graph, sampling=sample is not None)
-                    if sample is not None:               # its counters go on from the cache's position: the seed's sequence
-                        plain.sample.copy_(sample)
-                    plain.begin(torch.tensor([new[-1]], device=self.device))
-                emitted = [int(plain.step()[0])]
-                plain_steps += 1
-            for j, t in enumerate(emitted):
-                if j and stopped():                          # (before the step's first token the loop has tested already)
-                    done = True
-                    break
-                new.append(t)
-                if len(new) == max_new_tokens:
-                    break
-        ops.sk_poll_async(self.device)
-        torch.cuda.current_stream().synchronize()
-        ops.sk_check_polled(self.device)
-        for s_ in (sess, plain):
-            if s_ is not None:
-                s_.check()
-        seq = torch.cat([input_ids, torch.tensor([new], dtype=input_ids.dtype, device=self.device)], dim=1)
-        speculation = sess.speculation() if sess is not None else {"steps": 0, "drafted": 0, "accepted": 0}
-        speculation["steps"] += plain_steps                  # decode steps of either kind: steps + accepted = tokens they emitted
-        if prefix is not None:
-            prefix.settle(seq)
-        return seq, speculation
-
-    def _prefill(self, prefix, input_ids, images, attention_mask, B, S, ctx, max_new_tokens):
-        """The cache of a generation and the forward that fills it: a new cache and the whole prompt, or — with a
-        PrefixSession — the session's cache, the tokens behind its common prefix, and room for the new tokens."""
-        if prefix is None:
-            cache = self.model.llama.new_cache(B, max(ctx, S + 1))
-            return cache, self.forward(input_ids=input_ids, images=images, attention_mask=attention_mask, past_key_values=cache,
-                                       use_cache=True)
-        out = prefix.forward(input_ids, images)
-        prefix.reserve(S + max_new_tokens)
-        return prefix.cache, out
-
-    @staticmethod
-    def _processor_table(proc, S: int, eos_ids, device) -> Optional[torch.Tensor]:
-        """HF's processors of ``generate`` as one row of ops.processor_rows (checked with HF's messages), or None when none
-        of them would act (HF adds no processor: the decode is exactly the one without them)."""
-        if proc is None or all(a is None for a in proc):
-            return None
-        rp, nr, ml, mn = proc
-        table = ops.processor_rows(rp, nr, ml, mn, prompt_len=S)
-        if not eos_ids:
-            table[:, 2] = 0                                  # HF's minimum lengths need an EOS id
-        if bool((table.view(torch.float32)[:, 0] == 1.0).all() and (table[:, 1] == 0).all() and (table[:, 2] <= S).all()):
-            return None
-        return table.to(device)
-
-    def _generate(self, input_ids, images, attention_mask, max_new_tokens, do_sample, temperature, stopping_criteria, eos_token_id,
-                  use_graph, top_k, top_p, seed, proc=None, logprobs=None, lp_out=None, prefix=None, **kw):
-        input_ids = input_ids.to(self.device)
-        B, S = input_ids.shape
-        ctx = min(getattr(self.config, "max_position_embeddings", 2048), S + max_new_tokens)
-        cache, out = self._prefill(prefix, input_ids, images, attention_mask, B, S, ctx, max_new_tokens)
-        greedy = not (do_sample and temperature >= ops.GREEDY_T)
-        sample = None                                        # per-row parameters of the on-device draw
-        if not greedy and (top_k is not None or top_p is not None or seed is not None):
-            if seed is None:
-                seed = int(torch.randint(0, 1 << 62, (1,)).item())       # reproducible under torch.manual_seed
-            seeds = [(int(seed) + r) % (1 << 64) for r in range(B)] if not isinstance(seed, (list, tuple)) else list(seed)
-            if len(seeds) != B:
-                raise ValueError(f"generate: {len(seeds)} seeds for {B} rows")
-            sample = ops.sampling_rows(float(temperature), 0 if top_k is None else top_k, 1.0 if top_p is None else top_p,
-                                       seeds, device=self.device)
-
-        def pick(last, ctr):
-            if sample is not None:                           # ctr: index of the drawn token in the sequence
-                return ops.argmax(last, sampling=sample, ctr_add=ctr).to(torch.long)
-            return ops.argmax(last).to(torch.long) if greedy else \
-                torch.multinomial(torch.softmax(last / temperature, dim=-1), num_samples=1).view(B)
-
-        eos = None
-        if eos_token_id is not None:
-            eos = torch.as_tensor([eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id), device=self.device)
-        pad = kw.get("pad_token_id", getattr(self.config, "pad_token_id", None))
-        if pad is None:
-            pad = int(eos[0]) if eos is not None else 0
-        finished = torch.zeros((B,), dtype=torch.bool, device=self.device)     # HF: a finished row emits pad from then on
-        table = self._processor_table(proc, S, None if eos is None else eos.tolist(), self.device)
-        eos32 = hist = None
-        if table is not None:
-            table = table.expand(B, 4).contiguous()
-        last = out.logits[:, -1, :].contiguous()
-        lp_cols, lp_done = [], []                            # per new token: its [B, 1(, n)] record; the rows already finished
-
-        def score_raw(x):
-            """lse and top-n of the raw logits, before the processors and the sampler rewrite them in place (then: a copy)"""
-            raw = torch.empty_like(x) if (table is not None or sample is not None) else None
-            _, lse, tid, tl = ops.token_logprobs(x, top=logprobs, copy=raw)
-            return (x if raw is None else raw), lse, tid, tl
-
-        def record(scored, tok):
-            raw, lse, tid, tl = scored
-            col = torch.zeros((B, 1), dtype=torch.float32, device=self.device)
-            tabs = None
-            if logprobs:
-                tabs = (torch.full((B, 1, logprobs), -1, dtype=torch.int32, device=self.device),
-                        torch.zeros((B, 1, logprobs), dtype=torch.float32, device=self.device))
-            ops.score_record(raw, lse, tok.to(torch.int32), col, None, 0, top=(tid, tl) if logprobs else None, top_tables=tabs)
-            lp_cols.append((col,) + (tabs or ()))
-            lp_done.append(finished.clone())
-
-        scored = score_raw(last) if logprobs is not None else None
-        if table is not None:                                # HF's processors over each row's whole input_ids, on the device
-            eos32 = None if eos is None else eos.to(torch.int32)
-            hist = torch.zeros((B, cache.ctx_max), dtype=torch.int32, device=self.device)
-            hist[:, :S] = input_ids.to(torch.int32)
-            ops.logits_process(last, table, hist, None, S, None, eos32)
-        token = pick(last, S)
-        if logprobs is not None:                             # the first token: from the prefill's last logits
-            record(scored, token)
-        seq = torch.cat([input_ids, token[:, None]], dim=1)
-        if B > 8 or self.model.precision == "fp32":
-            use_graph = None                                 # the GEMV decode session is bf16, for <= 8 sequences
-        sess = None
-        if use_graph is not None:
-            from .decode import DecodeSession
-            sess = DecodeSession(self.model.llama, cache, use_graph=bool(use_graph), sampling=sample is not None,
-                                 processors=table is not None, processor_eos=None if eos is None else eos.tolist(),
-                                 **({} if logprobs is None else {"logprobs": logprobs}))
-            if sample is not None:
-                sess.sample.copy_(sample)
-            if table is not None:
-                sess.proc.copy_(table)
-            sess.begin(token, prompt_ids=input_ids if table is not None else None)
-        mask = attention_mask
-        for _ in range(max_new_tokens - 1):
-            if eos is not None:
-                finished |= torch.isin(token, eos)
-            if stopping_criteria is not None:
-                # HF StoppingCriteriaList: generation stops as soon as ANY criterion fires; a criterion may answer
-                # per row (bool tensor [B]) or for the whole batch (python bool, as the reference's keyword criterion)
-                for c in stopping_criteria:
-                    r = c(seq, None)
-                    finished |= r.to(self.device).view(-1) if isinstance(r, torch.Tensor) else torch.full_like(finished, bool(r))
-            if bool(finished.all()) or cache.seq_len + 1 > cache.ctx_max:
-                break
-            if sess is not None:
-                nxt = sess.step()
-                if greedy or sample is not None:
-                    token = nxt.to(torch.long).clone()
-                else:
-                    token = pick(sess.logits[:, :self.model.llama.V], None)
-                if bool(finished.any()) or not (greedy or sample is not None):
-                    token = torch.where(finished, torch.full_like(token, pad), token)
-                    sess.tok.copy_(token.to(torch.int32))
-                    if logprobs is not None and not (greedy or sample is not None):
-                        sess.record_token()                  # the step recorded its own argmax: the host's draw replaces it
-                if logprobs is not None:
-                    lp_done.append(finished.clone())
-            else:
-                if mask is not None:
-                    mask = torch.cat([mask.to(self.device), torch.ones((B, 1), dtype=mask.dtype, device=self.device)], dim=1)
-                out = self.forward(input_ids=token[:, None], attention_mask=mask, past_key_values=cache, use_cache=True)
-                last = out.logits[:, -1, :].contiguous()
-                scored = score_raw(last) if logprobs is not None else None
-                if table is not None:                        # the fed token joins the history at index seq_len - 1
-                    ops.logits_process(last, table, hist, None, cache.seq_len, token.to(torch.int32), eos32)
-                token = torch.where(finished, torch.full_like(token, pad), pick(last, cache.seq_len))
-                if logprobs is not None:
-                    record(scored, token)
-            seq = torch.cat([seq, token[:, None]], dim=1)
-        ops.sk_poll_async(self.device)
-        torch.cuda.current_stream().synchronize()            # the caller decodes the tokens next; a stream-K hand-off
-        ops.sk_check_polled(self.device)                     # failure anywhere in this generation is reported here at the latest
-        if sess is not None:
-            sess.check()                                     # ticket counters / grid-barrier abort word of the decode launches
-        if logprobs is not None:                             # one read of the session's tables, after the loop
-            new = seq.shape[1] - S
-            parts = [torch.cat([c[k] for c in lp_cols], dim=1) for k in range(3 if logprobs else 1)]
-            if sess is not None:                             # columns S + 1 ..: the tokens the steps chose
-                tabs = [sess.lp_table] + list(sess.lp_top_tables or ())
-                parts = [torch.cat([p, t[:, S + 1:S + new]], dim=1) for p, t in zip(parts, tabs)]
-            done = torch.stack(lp_done, dim=1)               # [B, new]: the row had finished before this token (a pad)
-            lp_out["token_logprobs"] = torch.where(done, torch.zeros_like(parts[0]), parts[0])
-            if logprobs:
-                lp_out["top_tokens"] = torch.where(done[:, :, None], torch.full_like(parts[1], -1), parts[1])
-                lp_out["top_logprobs"] = torch.where(done[:, :, None], torch.zeros_like(parts[2]), parts[2])
-        if prefix is not None:
-            prefix.settle(seq)
-        return seq
-
-    def _generate_beams(self, input_ids, images, attention_mask, max_new_tokens, nb, length_penalty, early_stopping, nrs,
-                        stopping_criteria, eos_token_id, use_graph, pad, proc=None):
-        """Beam search (HF ``_beam_search``): the B prompts are prefilled once (images, padding mask) into rows [0, B) of a
-        B * nb-row cache, whose prompt positions the reorder kernel then copies into every beam row (key_valid likewise).
-        Every step picks the K best continuations per prompt on the device (ops.beam_candidates), selects the running beams
-        (ops.beam_select) and makes the KV rows of the generated positions follow their parents (ops.kv_beam_reorder); the
-        host keeps the hypotheses (valley_amd.beam) from one small copy of the candidates.  Up to 8 rows the step is the
-        decode session's (captured with ``use_graph=True``, eager with False); otherwise, or with ``use_graph=None``, it is
-        the generic forward followed by the same three kernels.  Stopping criteria are evaluated on the host over the
-        [B * K, cur_len + 1] candidate sequences, as HF does; they then hand the hit mask to the select kernel.
-        With processors (``proc``) every beam row keeps its token history on the device (following its parent, as its KV
-        rows do), HF's processors run on log_softmax(logits) and the candidates are taken over those scores."""
-        from .beam import BeamSearch
-        from .decode import DecodeSession
-        input_ids = input_ids.to(self.device)
-        B, S = input_ids.shape
-        R, d = B * nb, self.device
-        ll = self.model.llama
-        eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id])
-        max_len = min(getattr(self.config, "max_position_embeddings", 2048), S + max_new_tokens)
-        if max_len <= S:
-            return input_ids.clone(), torch.zeros((B * nrs,), dtype=torch.float32)
-        state = BeamSearch(input_ids, nb, max_len, eos_ids=eos, pad_token_id=pad, length_penalty=length_penalty,
-                           early_stopping=early_stopping, num_return_sequences=nrs)
-        K = state.K
-        if state.K > ops.BEAM_MAX_K or nb > ops.BEAM_MAX_NB:
-            raise ValueError(f"beam search takes num_beams <= {ops.BEAM_MAX_NB} and max(2, 1 + n_eos) * num_beams <= "
-                             f"{ops.BEAM_MAX_K} (got {nb} beams, {len(eos)} EOS ids)")
-        cache = ll.new_cache(R, max_len + 1)
-        prompt = type(cache).rows_of(cache, 0, B)            # (HipKVCache, or the fp32 engine's F32KVCache)
-        out = self.forward(input_ids=input_ids, images=images, attention_mask=attention_mask, past_key_values=prompt,
-                           use_cache=True)
-        expand = torch.arange(R, dtype=torch.int32, device=d) // nb          # row b * nb + j <- prompt row b
-        kv_table = ops.kv_beam_table(cache.k, cache.v, d)
-        ops.kv_beam_reorder(kv_table, cache.k[0], expand, 0, S)
-        cache.seq_len = S
-        if prompt.key_valid is not None:
-            cache.key_valid = prompt.key_valid.index_select(0, expand.long()).contiguous()
-        eos_dev = torch.tensor(eos, dtype=torch.int32, device=d) if eos else None
-        scratch = ops.beam_scratch(B, nb, K, d)
-        running = state.initial_running().to(d)
-        first = out.logits[:, -1, :].float().repeat_interleave(nb, dim=0).contiguous()
-        table = self._processor_table(proc, S, eos, d)
-        hist = None
-        if table is None:
-            cand = ops.beam_candidates(first, running, B, nb, K, eos_dev, scratch)
-        else:                                                # HF: processors over log_softmax(logits), then + running
-            table = table.expand(R, 4).contiguous()
-            hist = torch.zeros((R, cache.ctx_max), dtype=torch.int32, device=d)
-            hist[:, :S] = input_ids.to(torch.int32).repeat_interleave(nb, dim=0)
-            ops.logits_process(first, table, hist, None, S, None, eos_dev, log_softmax=True)
-            cand = ops.logits_beam_candidates(first, running, B, nb, K, eos_dev, scratch)
-        host_crit = stopping_criteria is not None and len(stopping_criteria) > 0
-        if self.model.precision == "fp32" or R > 8:
-            use_graph = None                                 # the GEMV decode session: 16-bit storage, <= 8 rows
-        sess = None
-        if use_graph is not None:
-            sess = DecodeSession(ll, cache, use_graph=bool(use_graph), beams=(B, nb, S, eos, not host_crit),
-                                 processors=table is not None)
-            if table is not None:
-                sess.proc.copy_(table)
-
-        def finish_step(c):
-            """the host half of a step: hits (EOS, the caller's criteria), the host state; the hit mask goes back to the
-            device when a criterion added hits"""
-            seqs = state.candidates(c[0], c[1], c[2])
-            hits = c[3].to("cpu", torch.bool).view(-1)
-            added = False
-            for crit in (stopping_criteria if host_crit else ()):
-                r = crit(seqs.to(d), None)
-                new = r.to("cpu", torch.bool).view(-1) if isinstance(r, torch.Tensor) else torch.full_like(hits, bool(r))
-                added |= bool((new & ~hits).any())
-                hits = hits | new
-            state.advance(hits)
-            if added:
-                c[3].copy_(hits.to(torch.uint8).to(d))
-
-        finish_step(cand)
-        if sess is not None and not state.done:
-            ops.beam_select(*cand, B, nb, tok=sess.tok, parent=sess.parent, running=sess.running)
-            sess.begin(sess.tok.clone(), prompt_ids=hist[:, :S] if hist is not None else None)   # (nothing to reorder yet)
-        while not state.done:
-            if sess is not None:
-                sess.step()                                  # forward + candidates (+ select, reorder, pos += 1 without criteria)
-                finish_step(sess.cand)
-                if host_crit and not state.done:
-                    sess.beam_tail()
-            else:
-                tok, parent, running = ops.beam_select(*cand, B, nb, running=running)
-                if cache.seq_len > S:                        # the generated positions follow their parents
-                    ops.kv_beam_reorder(kv_table, cache.k[0], parent, S, cache.seq_len)
-                    if hist is not None:
-                        ops.logits_history_gather(hist, parent, S, cache.seq_len)
-                if cache.seq_len + 1 > cache.ctx_max:
-                    break
-                out = self.forward(input_ids=tok.to(torch.long)[:, None], past_key_values=cache, use_cache=True)
-                if hist is None:
-                    cand = ops.beam_candidates(out.logits[:, -1, :], running, B, nb, K, eos_dev, scratch)
-                else:
-                    x = out.logits[:, -1, :]
-                    ops.logits_process(x, table, hist, None, cache.seq_len, tok, eos_dev, log_softmax=True)
-                    cand = ops.logits_beam_candidates(x, running, B, nb, K, eos_dev, scratch)
-                finish_step(cand)
-        torch.cuda.current_stream().synchronize()
-        if sess is not None:
-            sess.check()
-        seq, scores = state.result()
-        return seq.to(d), scores
 
     # -- tokenizer / prompt glue -----------------------------------------------------------------------
     def resize_token_embeddings(self, n: int):
