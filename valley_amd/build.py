@@ -30,6 +30,7 @@ LIB_SPEC = os.path.join(LIBDIR, "libvalley_hip_spec.so")                   # pro
 LIB_SPEC_SAMPLE = os.path.join(LIBDIR, "libvalley_hip_spec_sample.so")     # the verify step's draw counters under seeded sampling
 LIB_SPEC_ROWS = os.path.join(LIBDIR, "libvalley_hip_spec_rows.so")         # the verify step of several sequences, one position each
 LIB_SUFFIX = os.path.join(LIBDIR, "libvalley_hip_suffix.so")               # split attention of 1..64 new queries over a cached prefix
+LIB_CONSTRAIN = os.path.join(LIBDIR, "libvalley_hip_constrain.so")         # token constraints: bad words, suppressed ids, forced EOS, tries
 # the C prologue every companion compiles (error text, launch check, the version / last-error entry points)
 COMPANION_SHARED = ["companion_capi.hpp"]
 
@@ -64,7 +65,11 @@ COMPANIONS_ROWS = (
 COMPANIONS_SUFFIX = (
     Companion("suffix", LIB_SUFFIX, ("suffix.hip",), "valley_hip_suffix.h", ("common.hpp",)),
 )
-ALL_COMPANIONS = (*COMPANIONS, *COMPANIONS_ROWS, *COMPANIONS_SUFFIX)
+# token constraints: a fourth table, walked by the same code (the three above are what the other libraries' tests count)
+COMPANIONS_CONSTRAIN = (
+    Companion("constrain", LIB_CONSTRAIN, ("constrain.hip",), "valley_hip_constrain.h", ()),
+)
+ALL_COMPANIONS = (*COMPANIONS, *COMPANIONS_ROWS, *COMPANIONS_SUFFIX, *COMPANIONS_CONSTRAIN)
 SOURCES = ["capi.hip", "gemm_bf16.hip", "gemm_p32.hip", "gemm_p16.hip", "gemm_streamk.hip", "norm_elementwise.hip", "attention.hip", "temporal_delta.hip", "preprocess.hip", "gemv_bf16.hip", "precise_f32.hip", "gemm_skinny.hip", "decode_step.hip", "sampling.hip"]
 
 

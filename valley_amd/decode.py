@@ -68,7 +68,7 @@ def _gemv_residual(sess, a, L, name):
 class DecodeSession:
     def __init__(self, llama: HipLlama, cache: HipKVCache, use_graph: bool = True, per_row_positions: bool = False,
                  sampling: bool = False, beams: Optional[tuple] = None, processors: bool = False,
-                 processor_eos: Optional[Sequence[int]] = None, logprobs: Optional[int] = None):
+                 processor_eos: Optional[Sequence[int]] = None, logprobs: Optional[int] = None, constraints=None):
         """``per_row_positions``: every batch row is an independent sequence at its own position (``pos`` is int32 [B]
         and advances by one per step for every row) — the captured step of valley_amd.serving.ContinuousBatcher.
         ``sampling``: the step draws each row's next token with that row's parameters in ``self.sample`` (int32 [B, 6],
@@ -94,7 +94,12 @@ class DecodeSession:
         log-probabilities in ``self.lp_top_tables`` (int32 / fp32 [B, ctx_max + 1, n]):
         ops.token_logprobs right behind the lm_head, ops.score_record behind the argmax / draw.  The processors and the
         sampler rewrite the logits in place before the token is known, so with either the raw row is copied aside
-        (``self.lp_raw``).  A token the caller picks itself (host sampling) is recorded by ``record_token()``."""
+        (``self.lp_raw``).  A token the caller picks itself (host sampling) is recorded by ``record_token()``.
+        ``constraints`` (an ops.ConstraintTables): the token constraints — bad words, suppressed and begin-suppressed ids, the
+        forced EOS, allowed-sequence tries — run right behind the processors' launch (ops.constrain), before the argmax /
+        draw / beam candidates, with each row's parameters in ``self.con`` (int32 [B, 4], ops.constraint_rows; all rows
+        neutral until written).  It implies ``processors`` (that launch appends the fed token to the history the constraints
+        read; its rows stay neutral unless written).  Rows, table contents and counts are read at every replay."""
         self.ll, self.cache = llama, cache
         B, d = cache.batch, llama.device
         if B > 8:
@@ -154,6 +159,10 @@ class DecodeSession:
             self.kv_table = None
             self._kv_table_gen = None
         self.proc = self.hist = self.proc_eos = None
+        self.con, self.con_tables = None, constraints
+        if constraints is not None:
+            processors = True
+            self.con = ops.constraint_rows(constraints, B, flags=0, device=d)
         if processors:
             self.proc = ops.processor_rows([None] * B, device=d)
             self.hist = torch.zeros((B, cache.ctx_max), dtype=torch.int32, device=d)
@@ -224,6 +233,8 @@ class DecodeSession:
                 ops.logits_history_gather(self.hist, self.parent, S, 0, len_dev=self.pos)
                 ops.logits_process(self.logits[:, :ll.V], self.proc, self.hist, self.pos, 1, tok=self.tok, eos=self.proc_eos,
                                    log_softmax=True)
+                if self.con is not None:
+                    ops.constrain(self.logits[:, :ll.V], self.con, self.con_tables, self.hist, self.pos, 1)
                 ops.logits_beam_candidates(self.logits[:, :ll.V], self.running, bB, nb, K, self.eos, self.bscratch,
                                            out=self.cand)
             if tail:
@@ -233,6 +244,8 @@ class DecodeSession:
             ops.token_logprobs(self.logits[:, :ll.V], top=self.lp_n, out_lse=self.lp_lse, copy=self.lp_raw, out_top=self.lp_top)
         if self.proc is not None:                    # the token fed to this step joins the history at index pos
             ops.logits_process(self.logits[:, :ll.V], self.proc, self.hist, self.pos, 1, tok=self.tok, eos=self.proc_eos)
+        if self.con is not None:                     # behind the append: the constraints read the history up to the fed token
+            ops.constrain(self.logits[:, :ll.V], self.con, self.con_tables, self.hist, self.pos, 1)
         if self.sample is None:
             ops.argmax(self.logits[:, :ll.V], out=self.tok)
         else:

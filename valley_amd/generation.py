@@ -65,6 +65,45 @@ def processor_table(proc, S: int, eos, device, rows: int = 1):
     return table.to(device).expand(rows, 4).contiguous()
 
 
+def constraint_setup(con, V: int, S: int, max_new_tokens: int, eos, device, rows: int = 1, beams: bool = False):
+    """``generate``'s token constraints — ``con`` = (bad_words_ids, suppress_tokens, begin_suppress_tokens, forced_eos_token_id,
+    allowed_sequences) — as (ops.ConstraintTables, int32 [rows, 4] rows of ops.constraint_rows) on ``device``, or None when none
+    was given.  Checked before anything is launched, with HF's messages where HF has one.  ``forced_eos_token_id`` (an int or a
+    list) is HF's: at length S + max_new_tokens - 1 only those ids remain; it has to name the ``eos`` ids, the one EOS table of
+    every rule.  ``allowed_sequences``: token-id lists shared by all rows, or one such list of lists per row."""
+    if con is None or all(a is None for a in con):
+        return None
+    bad, sup, beg, forced, allowed = con
+    if beams and (allowed is not None or forced is not None):
+        raise ValueError("allowed_sequences and forced_eos_token_id are not supported with num_beams > 1 (a row that is all "
+                         "-inf but a few ids changes which ties the beams' top-K picks); bad_words_ids, suppress_tokens and "
+                         "begin_suppress_tokens are")
+    if forced is not None:
+        if not eos:
+            raise ValueError("`forced_eos_token_id` needs an `eos_token_id`: the ids it forces are the generation's EOS ids")
+        if isinstance(forced, bool) or not isinstance(forced, (int, list, tuple)) or sorted(set(eos_ids(forced))) != sorted(set(eos)):
+            raise ValueError(f"`forced_eos_token_id` has to name the `eos_token_id` ids {sorted(set(eos))} (one EOS table serves "
+                             f"every rule), but is {forced}")
+    if allowed is not None and not eos:
+        raise ValueError("`allowed_sequences` needs an `eos_token_id`: behind a complete sequence only EOS is allowed")
+    per_row, tries = False, []
+    if allowed is not None:
+        if not isinstance(allowed, (list, tuple)) or len(allowed) == 0:
+            raise ValueError(f"`allowed_sequences` has to be a non-empty list of lists, but is {allowed}.")
+        first = allowed[0]
+        per_row = isinstance(first, (list, tuple)) and len(first) > 0 and isinstance(first[0], (list, tuple))
+        if per_row and len(allowed) != rows:
+            raise ValueError(f"allowed_sequences: {len(allowed)} per-row lists for {rows} rows")
+        tries = list(allowed) if per_row else [allowed]
+        words = [len(ops.pack_trie(t, V)) for t in tries]    # validates every sequence
+    cap = {"trie": max(words), "trie_slots": len(tries)} if tries else None
+    tables = ops.constraint_tables(bad, sup, beg, eos=eos or None, V=V, capacity=cap, device=device)
+    roots = [ops.constraint_trie(tables, i, t) for i, t in enumerate(tries)]
+    root = -1 if not roots else (roots if per_row else roots[0])
+    return tables, ops.constraint_rows(tables, rows, begin=S, max_length=S + max_new_tokens if forced is not None else 0,
+                                       trie_root=root, device=device)
+
+
 def score_raw(x, n: int, rewritten: bool):
     """(raw logits, lse, top-n ids, top-n values) of ``x``; the raw logits are a copy when processors or a sampler will rewrite ``x``.
     The first token is, in every caller: score_raw -> ops.logits_process -> ops.argmax (counter S) -> ops.score_record of the token."""
@@ -155,12 +194,13 @@ def _generate_spec(model, input_ids, images, attention_mask, max_new_tokens, sto
 
 
 def _generate(model, input_ids, images, attention_mask, max_new_tokens, do_sample, temperature, stopping_criteria, eos_token_id,
-              use_graph, top_k, top_p, seed, pad, proc=None, logprobs=None, prefix=None):
+              use_graph, top_k, top_p, seed, pad, proc=None, logprobs=None, prefix=None, con=None):
     """Greedy decoding and sampling: the first token from the prefill's logits, then one ``step`` per token (the decode session's, or
     the generic forward's) until every row has finished; a finished row emits ``pad`` (HF).  -> sequences, log-probability fields."""
     d = model.device
     input_ids = input_ids.to(d)
     B, S = input_ids.shape
+    con = constraint_setup(con, model.model.llama.V, S, max_new_tokens, eos_ids(eos_token_id), d, B)
     cache, out = _prefill(model, prefix, input_ids, images, attention_mask, B, S, max_new_tokens)
     greedy = not (do_sample and temperature >= ops.GREEDY_T)
     sample = None                                            # per-row parameters of the on-device draw
@@ -184,6 +224,8 @@ def _generate(model, input_ids, images, attention_mask, max_new_tokens, do_sampl
         pad = int(eos[0]) if eos is not None else 0
     finished = torch.zeros((B,), dtype=torch.bool, device=d)
     table = processor_table(proc, S, eos_list, d, B)
+    if con is not None and table is None:                    # the constraints read the history the processors' launch appends to
+        table = ops.processor_rows([None] * B, device=d)
     rewritten = table is not None or sample is not None      # the logits are rewritten in place before the token is picked
     lp_cols, lp_done = [], []                                # per new token: its [B, 1(, n)] record; the rows already finished
 
@@ -203,6 +245,8 @@ def _generate(model, input_ids, images, attention_mask, max_new_tokens, do_sampl
         hist = torch.zeros((B, cache.ctx_max), dtype=torch.int32, device=d)
         hist[:, :S] = input_ids.to(torch.int32)
         ops.logits_process(last, table, hist, None, S, None, eos32)
+        if con is not None:
+            ops.constrain(last, con[1], con[0], hist, None, S)
     token = pick(last, S)
     if logprobs is not None:                                 # the first token: from the prefill's last logits
         record(scored, token)
@@ -213,11 +257,14 @@ def _generate(model, input_ids, images, attention_mask, max_new_tokens, do_sampl
     if use_graph is not None:
         from .decode import DecodeSession
         sess = DecodeSession(model.model.llama, cache, use_graph=bool(use_graph), sampling=sample is not None, processors=table is not None,
-                             processor_eos=eos_list, **({} if logprobs is None else {"logprobs": logprobs}))
+                             processor_eos=eos_list, **({} if logprobs is None else {"logprobs": logprobs}),
+                             **({} if con is None else {"constraints": con[0]}))
         if sample is not None:
             sess.sample.copy_(sample)
         if table is not None:
             sess.proc.copy_(table)
+        if con is not None:
+            sess.con.copy_(con[1])
         sess.begin(token, prompt_ids=input_ids if table is not None else None)
 
     def session_step(token):
@@ -240,6 +287,8 @@ def _generate(model, input_ids, images, attention_mask, max_new_tokens, do_sampl
         scored = score_raw(last, logprobs, rewritten) if logprobs is not None else None
         if table is not None:                                # the fed token joins the history at index seq_len - 1
             ops.logits_process(last, table, hist, None, cache.seq_len, token.to(torch.int32), eos32)
+            if con is not None:
+                ops.constrain(last, con[1], con[0], hist, None, cache.seq_len)
         token = torch.where(finished, torch.full_like(token, pad), pick(last, cache.seq_len))
         if logprobs is not None:
             record(scored, token)
@@ -273,7 +322,7 @@ def _generate(model, input_ids, images, attention_mask, max_new_tokens, do_sampl
 
 
 def _generate_beams(model, input_ids, images, attention_mask, max_new_tokens, nb, length_penalty, early_stopping, nrs,
-                    stopping_criteria, eos_token_id, use_graph, pad, proc=None):
+                    stopping_criteria, eos_token_id, use_graph, pad, proc=None, con=None):
     """Beam search (HF ``_beam_search``): the B prompts are prefilled once (images, padding mask) into rows [0, B) of a B * nb-row
     cache, whose prompt positions the reorder kernel then copies into every beam row (key_valid likewise).  Every step picks the K
     best continuations per prompt on the device (ops.beam_candidates), selects the running beams (ops.beam_select) and makes the KV
@@ -290,6 +339,7 @@ def _generate_beams(model, input_ids, images, attention_mask, max_new_tokens, nb
     R, ll = B * nb, model.model.llama
     eos = eos_ids(eos_token_id)
     max_len = context_limit(model.config, S, max_new_tokens)
+    con = constraint_setup(con, ll.V, S, max_new_tokens, eos, d, R, beams=True)
     if max_len <= S:
         return input_ids.clone(), torch.zeros((B * nrs,), dtype=torch.float32)
     state = BeamSearch(input_ids, nb, max_len, eos_ids=eos, pad_token_id=pad, length_penalty=length_penalty,
@@ -312,6 +362,8 @@ def _generate_beams(model, input_ids, images, attention_mask, max_new_tokens, nb
     running = state.initial_running().to(d)
     first = out.logits[:, -1, :].float().repeat_interleave(nb, dim=0).contiguous()
     table = processor_table(proc, S, eos, d, R)
+    if con is not None and table is None:                    # the constraints run behind the processors' launch, on its scores
+        table = ops.processor_rows([None] * R, device=d)
     hist = None
     if table is not None:                                    # every beam row's history: its prompt's whole input_ids
         hist = torch.zeros((R, cache.ctx_max), dtype=torch.int32, device=d)
@@ -322,6 +374,8 @@ def _generate_beams(model, input_ids, images, attention_mask, max_new_tokens, nb
         if table is None:
             return ops.beam_candidates(x, running, B, nb, K, eos_dev, scratch)
         ops.logits_process(x, table, hist, None, length, tok, eos_dev, log_softmax=True)
+        if con is not None:
+            ops.constrain(x, con[1], con[0], hist, None, length)
         return ops.logits_beam_candidates(x, running, B, nb, K, eos_dev, scratch)
 
     def finish_step(c):
@@ -340,9 +394,12 @@ def _generate_beams(model, input_ids, images, attention_mask, max_new_tokens, nb
         use_graph = None                                     # the GEMV decode session: 16-bit storage, <= 8 rows
     sess = None
     if use_graph is not None:
-        sess = DecodeSession(ll, cache, use_graph=bool(use_graph), beams=(B, nb, S, eos, not host_crit), processors=table is not None)
+        sess = DecodeSession(ll, cache, use_graph=bool(use_graph), beams=(B, nb, S, eos, not host_crit), processors=table is not None,
+                             **({} if con is None else {"constraints": con[0]}))
         if table is not None:
             sess.proc.copy_(table)
+        if con is not None:
+            sess.con.copy_(con[1])
     finish_step(cand)
     if sess is not None and not state.done:
         ops.beam_select(*cand, B, nb, tok=sess.tok, parent=sess.parent, running=sess.running)

@@ -1519,6 +1519,232 @@ def logits_beam_candidates(scores: torch.Tensor, running: torch.Tensor, B: int, 
     return out
 
 
+# ---- token constraints (libvalley_hip_constrain.so, include/valley_hip_constrain.h) ------------------------------------------
+CONSTRAIN_MAX_WORD = 64      # VLY_CONSTRAIN_MAX_WORD
+CONSTRAIN_MAX_DEPTH = 64     # VLY_CONSTRAIN_MAX_DEPTH
+CONSTRAIN_HEADER = 16        # VLY_CONSTRAIN_HEADER
+CONSTRAIN_BAD_WORDS, CONSTRAIN_TRIE, CONSTRAIN_FORCED_EOS, CONSTRAIN_SUPPRESS, CONSTRAIN_BEGIN_SUPPRESS = 1, 2, 4, 8, 16
+
+
+def _id_list(name, ids, V, what="a non-empty list of integers"):
+    """A suppress / EOS list as python ints in [0, V)."""
+    if isinstance(ids, torch.Tensor):
+        ids = ids.reshape(-1).tolist()
+    if not isinstance(ids, (list, tuple)) or len(ids) == 0:
+        raise ValueError(f"`{name}` has to be {what}, but is {ids}.")
+    if any(isinstance(t, bool) or not isinstance(t, int) or t < 0 for t in ids):
+        raise ValueError(f"`{name}` has to be a list of positive integers, but is {ids}.")
+    bad = [t for t in ids if t >= V]
+    if bad:
+        raise ValueError(f"The model vocabulary size is {V}, but `{name}` holds the ids {bad}")
+    return [int(t) for t in ids]
+
+
+def pack_bad_words(bad_words_ids, eos, V) -> list:
+    """The words region of the constraint tables (valley_hip_constrain.h): n pairs {start, L}, then the words' tokens.
+    Checked as NoBadWordsLogitsProcessor checks them, with its messages; words equal to [eos] for an EOS id are dropped and
+    equal words kept once, as HF does.  -> (region words, number of words)."""
+    import numpy as np
+    if not isinstance(bad_words_ids, list) or len(bad_words_ids) == 0:
+        raise ValueError(f"`bad_words_ids` has to be a non-empty list, but is {bad_words_ids}.")
+    if any(not isinstance(w, list) for w in bad_words_ids):
+        raise ValueError(f"`bad_words_ids` has to be a list of lists, but is {bad_words_ids}.")
+    if any(any((not isinstance(t, (int, np.integer)) or isinstance(t, bool) or t < 0) for t in w) for w in bad_words_ids):
+        raise ValueError(f"Each list in `bad_words_ids` has to be a list of positive integers, but is {bad_words_ids}.")
+    if any(len(w) == 0 for w in bad_words_ids):
+        raise ValueError(f"Each list in `bad_words_ids` has to be a non-empty list of positive integers, but is {bad_words_ids}.")
+    invalid = [int(t) for w in bad_words_ids for t in w if t >= V]
+    if invalid:
+        raise ValueError(f"The model vocabulary size is {V}, but the following tokens were being biased: {invalid}")
+    long = [w for w in bad_words_ids if len(w) > CONSTRAIN_MAX_WORD]
+    if long:
+        raise ValueError(f"a bad word holds at most {CONSTRAIN_MAX_WORD} tokens, got one of {len(long[0])}")
+    words = list(dict.fromkeys(tuple(int(t) for t in w) for w in bad_words_ids if all(list(w) != [e] for e in (eos or ()))))
+    index, pool = [], []
+    for w in words:
+        index += [2 * len(words) + len(pool), len(w)]
+        pool += w
+    return index + pool, len(words)
+
+
+def pack_trie(allowed_sequences, V, base: int = 0) -> list:
+    """One trie of the constraint tables (valley_hip_constrain.h): nodes {n, ends, n pairs {token, child}} with the pairs
+    sorted by token, addressed by ``base`` + their word offset inside the returned list; the root is the first node.  Equal
+    sequences count once."""
+    if not isinstance(allowed_sequences, (list, tuple)) or len(allowed_sequences) == 0:
+        raise ValueError(f"`allowed_sequences` has to be a non-empty list of lists, but is {allowed_sequences}.")
+    root = {}
+    for s in allowed_sequences:
+        if isinstance(s, torch.Tensor):
+            s = s.reshape(-1).tolist()
+        if not isinstance(s, (list, tuple)) or len(s) == 0:
+            raise ValueError(f"Each sequence in `allowed_sequences` has to be a non-empty list of positive integers, but is {s}.")
+        if any(isinstance(t, bool) or not isinstance(t, int) or t < 0 for t in s):
+            raise ValueError(f"Each sequence in `allowed_sequences` has to be a non-empty list of positive integers, but is {s}.")
+        if any(t >= V for t in s):
+            raise ValueError(f"The model vocabulary size is {V}, but `allowed_sequences` holds the ids {[t for t in s if t >= V]}")
+        if len(s) > CONSTRAIN_MAX_DEPTH:
+            raise ValueError(f"an allowed sequence holds at most {CONSTRAIN_MAX_DEPTH} tokens, got one of {len(s)}")
+        node = root
+        for t in s:
+            node = node.setdefault("kids", {}).setdefault(int(t), {})
+        node["ends"] = 1
+    out, todo = [], [(root, None)]                            # (node, the word of its parent's pair that holds its offset)
+    while todo:
+        node, slot = todo.pop()
+        p = len(out)
+        if slot is not None:
+            out[slot] = base + p
+        kids = sorted(node.get("kids", {}).items())
+        out += [len(kids), node.get("ends", 0)]
+        for t, child in kids:
+            out += [t, -1]
+            todo.append((child, len(out) - 1))
+    return out
+
+
+class ConstraintTables:
+    """The shared device tables of ``constrain`` (int32, the layout of valley_hip_constrain.h): EOS ids, suppressed and
+    begin-suppressed ids, bad words, and ``trie_slots`` trie regions of ``trie_capacity`` words each.  ``write`` rewrites the
+    lists in place (a captured launch reads the new contents and counts), ``constraint_trie`` one trie region."""
+
+    def __init__(self, V: int, capacity: dict, device=None):
+        self.V = int(V)
+        cap = {k: int(capacity.get(k, 0)) for k in ("eos", "suppress", "begin", "words", "trie")}
+        self.trie_slots = int(capacity.get("trie_slots", 1))
+        if any(v < 0 for v in cap.values()) or self.trie_slots < 1:
+            raise ValueError(f"constraint_tables: bad capacity {capacity}")
+        self.capacity, self.trie_capacity = cap, cap["trie"]
+        self.off, o = {}, CONSTRAIN_HEADER
+        for k in ("eos", "suppress", "begin", "words", "trie"):
+            self.off[k] = o
+            o += cap[k] * (self.trie_slots if k == "trie" else 1)
+        head = torch.zeros((o,), dtype=torch.int32)
+        head[4:9] = torch.tensor([self.off[k] for k in ("eos", "suppress", "begin", "words", "trie")], dtype=torch.int32)
+        head[9], head[10] = cap["words"], cap["trie"] * self.trie_slots
+        self.buf = head.to(device) if device is not None else head
+        self.eos, self.n = [], {"eos": 0, "suppress": 0, "begin": 0, "words": 0}
+
+    def write(self, bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, eos=None) -> "ConstraintTables":
+        V = self.V
+        eos_l = [] if eos is None else _id_list("eos_token_id", [eos] if isinstance(eos, int) else eos, V)
+        regions = {"eos": eos_l,
+                   "suppress": [] if suppress_tokens is None else _id_list("suppress_tokens", suppress_tokens, V),
+                   "begin": [] if begin_suppress_tokens is None else _id_list("begin_suppress_tokens", begin_suppress_tokens, V)}
+        regions["words"], n_words = ([], 0) if bad_words_ids is None else pack_bad_words(bad_words_ids, eos_l, V)
+        for k, r in regions.items():
+            if len(r) > self.capacity[k]:
+                raise ValueError(f"constraint_tables: the {k} table takes {len(r)} words, its capacity is {self.capacity[k]}")
+        counts = [len(regions["eos"]), len(regions["suppress"]), len(regions["begin"]), n_words]
+        for k, r in regions.items():
+            if r:
+                self.buf[self.off[k]:self.off[k] + len(r)].copy_(torch.tensor(r, dtype=torch.int32))
+        self.buf[:4].copy_(torch.tensor(counts, dtype=torch.int32))
+        self.eos, self.n = eos_l, dict(zip(("eos", "suppress", "begin", "words"), counts))
+        return self
+
+    def flags(self) -> int:
+        """The rules the lists switch on for a row (the trie and the forced EOS are per row: ``constraint_rows``)."""
+        return (CONSTRAIN_BAD_WORDS if self.n["words"] else 0) | (CONSTRAIN_SUPPRESS if self.n["suppress"] else 0) | \
+            (CONSTRAIN_BEGIN_SUPPRESS if self.n["begin"] else 0)
+
+
+def constraint_tables(bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, eos=None, V=None, capacity=None,
+                      device=None) -> ConstraintTables:
+    """The shared tables of ``constrain`` on ``device``.  ``capacity``: None (the lists' own sizes, no trie region) or a dict
+    of words per region — "eos", "suppress", "begin", "words" (2 per bad word + its tokens), "trie" (per slot: 2 per node + 2
+    per edge, ``len(pack_trie(...))``), "trie_slots" (default 1); a region the dict leaves out gets its list's own size.
+    Refusals are HF's where HF has one (NoBadWordsLogitsProcessor's), raised before anything touches the device."""
+    if V is None or int(V) < 1:
+        raise ValueError("constraint_tables: V (the vocabulary size) is required")
+    need = _constraint_need(int(V), bad_words_ids, suppress_tokens, begin_suppress_tokens, eos)
+    cap = {**need, "trie": 0, "trie_slots": 1, **(capacity or {})}
+    return ConstraintTables(V, cap, device).write(bad_words_ids, suppress_tokens, begin_suppress_tokens, eos)
+
+
+def _constraint_need(V, bad_words_ids, suppress_tokens, begin_suppress_tokens, eos) -> dict:
+    """words each list needs (validates them, without a device)"""
+    eos_l = [] if eos is None else _id_list("eos_token_id", [eos] if isinstance(eos, int) else eos, V)
+    return {"eos": len(eos_l),
+            "suppress": 0 if suppress_tokens is None else len(_id_list("suppress_tokens", suppress_tokens, V)),
+            "begin": 0 if begin_suppress_tokens is None else len(_id_list("begin_suppress_tokens", begin_suppress_tokens, V)),
+            "words": 0 if bad_words_ids is None else len(pack_bad_words(bad_words_ids, eos_l, V)[0])}
+
+
+def constraint_trie(tables: ConstraintTables, root_slot: int, allowed_sequences) -> int:
+    """Write the trie of ``allowed_sequences`` into region ``root_slot`` of ``tables`` (in place: a captured launch walks the
+    new trie); returns the root, the ``trie_root`` of a row of ``constraint_rows``.  Needs an EOS id in the tables: a finished
+    sequence can only be followed by EOS."""
+    if not 0 <= int(root_slot) < tables.trie_slots:
+        raise ValueError(f"constraint_trie: slot {root_slot} of {tables.trie_slots}")
+    if not tables.eos:
+        raise ValueError("`allowed_sequences` needs an `eos_token_id`: behind a complete sequence only EOS is allowed")
+    base = int(root_slot) * tables.trie_capacity
+    words = pack_trie(allowed_sequences, tables.V, base)
+    if len(words) > tables.trie_capacity:
+        raise ValueError(f"constraint_tables: the trie takes {len(words)} words, a slot's capacity is {tables.trie_capacity}")
+    o = tables.off["trie"] + base
+    tables.buf[o:o + len(words)].copy_(torch.tensor(words, dtype=torch.int32))
+    return base
+
+
+def constraint_rows(tables: ConstraintTables, rows: int = 1, begin=0, max_length=0, trie_root=-1, flags=None,
+                    device=None) -> torch.Tensor:
+    """Per-row parameters of ``constrain`` as int32 [rows, 4]: {flags, begin, max_length, trie_root}.  ``begin`` (the prompt's
+    length), ``max_length`` (forced EOS at len == max_length - 1; 0 = off) and ``trie_root`` (``constraint_trie``'s; -1 = no
+    trie) are scalars or one value per row.  ``flags``: None — what ``tables`` holds plus the row's trie / forced EOS — or the
+    bits themselves.  ``constraint_rows(tables, R, flags=0)`` are neutral rows."""
+    def col(v, name):
+        v = v.reshape(-1).tolist() if isinstance(v, torch.Tensor) else v
+        v = list(v) if isinstance(v, (list, tuple)) else [v] * rows
+        if len(v) != rows or any(isinstance(a, bool) or not isinstance(a, int) for a in v):
+            raise ValueError(f"constraint_rows: {name} must be an int or {rows} ints, got {v}")
+        return v
+    if rows < 1:
+        raise ValueError("constraint_rows: no rows")
+    b, m, t = col(begin, "begin"), col(max_length, "max_length"), col(trie_root, "trie_root")
+    if any(a < 0 for a in b) or any(a < 0 for a in m) or any(a < -1 or a >= max(1, tables.trie_capacity * tables.trie_slots) for a in t):
+        raise ValueError(f"constraint_rows: begin >= 0, max_length >= 0 and -1 <= trie_root < the trie region expected, got {b} / {m} / {t}")
+    if any(a > 0 for a in m) and not tables.eos:
+        raise ValueError("`forced_eos_token_id` needs an EOS id in the constraint tables")
+    if any(a >= 0 for a in t) and not tables.eos:
+        raise ValueError("`allowed_sequences` needs an `eos_token_id`: behind a complete sequence only EOS is allowed")
+    if flags is None:
+        f = [tables.flags() | (CONSTRAIN_TRIE if t[r] >= 0 else 0) | (CONSTRAIN_FORCED_EOS if m[r] > 0 else 0) for r in range(rows)]
+    else:
+        f = col(flags, "flags")
+    out = torch.tensor([f, b, m, t], dtype=torch.int32).t().contiguous()
+    return out.to(device) if device is not None else out
+
+
+def constrain(logits: torch.Tensor, rows: torch.Tensor, tables: ConstraintTables, hist: torch.Tensor,
+              length: Optional[torch.Tensor] = None, len_add: int = 0) -> torch.Tensor:
+    """In place on logits fp32 [R, V] (row stride may exceed V): the token constraints of ``rows`` (int32 [R, 4],
+    ``constraint_rows``) and ``tables`` over the history ``hist`` (int32 [R, hist_ld]), behind ``logits_process`` (which has
+    appended the fed token).  Row r's length is ``length[r]`` (int32 [R]) or ``length[0]`` (int32 [1]), plus ``len_add``.
+    Everything is read on the device."""
+    from . import lib_constrain
+    _chk(logits, torch.float32, "logits", contiguous=False)
+    _chk(rows, torch.int32, "rows")
+    _chk(hist, torch.int32, "hist")
+    _chk(tables.buf, torch.int32, "tables")
+    R, V = logits.shape
+    if logits.stride(1) != 1 or tuple(rows.shape) != (R, 4) or hist.dim() != 2 or hist.shape[0] != R or V != tables.V:
+        raise ValueError(f"constrain: logits [R, {tables.V}] with unit column stride, rows [R, 4] and hist [R, L] expected, got "
+                         f"{tuple(logits.shape)} / {tuple(rows.shape)} / {tuple(hist.shape)}")
+    lptr, per_row = None, 0
+    if length is not None:
+        _chk(length, torch.int32, "length")
+        if length.numel() not in (1, R):
+            raise ValueError(f"constrain: length must hold 1 or {R} values, got {length.numel()}")
+        lptr, per_row = length.data_ptr(), int(length.numel() == R and R > 1)
+    rc = lib_constrain.load().vly_constrain_apply(logits.data_ptr(), logits.stride(0), V, R, rows.data_ptr(), tables.buf.data_ptr(),
+                                                  tables.buf.numel(), hist.data_ptr(), hist.shape[1], lptr, per_row, int(len_add),
+                                                  _stream())
+    lib_constrain.check(rc, "vly_constrain_apply")
+    return logits
+
+
 # ---- token log-probabilities and the forward-only loss (libvalley_hip_score.so, include/valley_hip_score.h) ----------------
 SCORE_MAX_TOP = 20       # VLY_SCORE_MAX_TOP
 SCORE_MAX_V = 1 << 18

@@ -112,7 +112,9 @@ class ContinuousBatcher:
 
     def __init__(self, model, slots: int = 4, ctx_max: int = 1024, use_graph: bool = True, sampling: bool = False,
                  processors: bool = False, eos_token_id=None, logprobs: Optional[int] = None,
-                 prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None):
+                 prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None,
+                 constraints: bool = False, bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None,
+                 trie_capacity: int = 4096):
         """``sampling``: the captured step draws every slot's token with the parameters ``add`` gave its request
         (temperature, top-k, top-p, seed; DecodeSession ``sampling``) — a seeded request's tokens then depend on its seed
         alone, not on its slot or its neighbours.  Greedy requests take the argmax in either kind of batcher.
@@ -131,7 +133,13 @@ class ContinuousBatcher:
         exactly the tokens the plain batcher would have returned over as many steps (greedy, or the request's seed's under
         ``sampling=True``, where a sampling request must bring its ``seed``).  EOS, stop criteria and max_new_tokens stay the
         caller's business: the caller truncates a step's list at its own stop and releases the slot.  Not with ``processors``
-        or ``logprobs``.  ``speculation(slot)`` reports the slot's {"steps", "drafted", "accepted"}."""
+        or ``logprobs``.  ``speculation(slot)`` reports the slot's {"steps", "drafted", "accepted"}.
+        ``constraints``: the captured step runs the token constraints (DecodeSession ``constraints``; ops.constrain).
+        ``bad_words_ids`` / ``suppress_tokens`` / ``begin_suppress_tokens`` are shared by all requests; ``add`` gives a request
+        its own ``allowed_sequences`` — written into the slot's region of ``trie_capacity`` int32 words (2 per trie node + 2 per
+        edge) between steps, without a re-capture — and its forced EOS.  ``eos_token_id`` is what ends an allowed sequence and
+        what the forced EOS leaves.  A request's tokens do not depend on its slot or its neighbours.  Not with
+        ``prompt_lookup_num_tokens``."""
         if not 1 <= slots <= 8:
             raise ValueError("1 <= slots <= 8 (the decode step streams weights with the GEMV kernels)")
         self.spec_k = None
@@ -145,6 +153,9 @@ class ContinuousBatcher:
                                  "one row per sequence)")
             if logprobs is not None:
                 raise ValueError("prompt_lookup_num_tokens does not combine with logprobs")
+            if constraints:
+                raise ValueError("prompt_lookup_num_tokens does not combine with constraints=True (the token constraints rewrite "
+                                 "the logits a draft is checked against)")
             from . import spec as _spec
             _spec.refuse_engine()
             self.spec_k, self.spec_ngram = k, n
@@ -159,12 +170,19 @@ class ContinuousBatcher:
         self.sampling = sampling
         self.processors = processors
         eos = eos_ids(eos_token_id)
+        if not constraints and any(a is not None for a in (bad_words_ids, suppress_tokens, begin_suppress_tokens)):
+            raise ValueError("bad_words_ids / suppress_tokens / begin_suppress_tokens need ContinuousBatcher(..., constraints=True)")
+        self.constraints = None                                  # the shared tables: one trie region per slot
+        if constraints:
+            self.constraints = ops.constraint_tables(bad_words_ids, suppress_tokens, begin_suppress_tokens, eos=eos or None, V=self.ll.V,
+                                                     capacity={"trie": int(trie_capacity), "trie_slots": slots}, device=self.ll.device)
         if self.spec_k is not None:
             self.sess = _spec.SpecRowsSession(self.ll, self.cache, self.spec_k, max_ngram=self.spec_ngram, eos_ids=eos,
                                               use_graph=use_graph, sampling=sampling)
         else:
             self.sess = DecodeSession(self.ll, self.cache, use_graph=use_graph, per_row_positions=True, sampling=sampling,
-                                      processors=processors, processor_eos=eos, **({} if logprobs is None else {"logprobs": logprobs}))
+                                      processors=processors, processor_eos=eos, **({} if logprobs is None else {"logprobs": logprobs}),
+                                      **({} if self.constraints is None else {"constraints": self.constraints}))
         self.logprobs = None if logprobs is None else int(logprobs)
         self.first_logprobs, self.last_logprobs = {}, {}
         self.live = [False] * slots
@@ -176,13 +194,16 @@ class ContinuousBatcher:
 
     def add(self, input_ids, images=None, attention_mask=None, first_token: Optional[int] = None, temperature: float = 0.0,
             top_k: int = 0, top_p: float = 1.0, seed: Optional[int] = None, repetition_penalty=None, no_repeat_ngram_size=None,
-            min_new_tokens=None) -> int:
+            min_new_tokens=None, allowed_sequences=None, forced_eos_at: Optional[int] = None) -> int:
         """Prefill one request (input_ids [1, S]) into a free slot; returns the slot.  The first generated token is the
         prefill's argmax unless ``first_token`` is given.  ``temperature`` >= 1e-4 (a sampling batcher only) makes the
         request sample: its first token is drawn on the device from the prefill's logits (draw counter S), the following
         ones inside the captured step; without a ``seed`` one is drawn from torch's generator.
         ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_new_tokens`` (a processor batcher only) are HF's
-        processors for this request, applied to the prefill's logits (its first token) and inside every step."""
+        processors for this request, applied to the prefill's logits (its first token) and inside every step.
+        ``allowed_sequences`` (token-id lists: the request answers with exactly one of them, then EOS) and ``forced_eos_at = n``
+        (its n-th new token can only be an EOS id: HF's forced EOS at max_new_tokens = n) need a constraints batcher, whose
+        shared lists apply to every request."""
         if temperature > 0 and not self.sampling:
             raise ValueError("add(temperature > 0) needs ContinuousBatcher(..., sampling=True)")
         params = None
@@ -203,12 +224,21 @@ class ContinuousBatcher:
         if self.processors:                                      # validates; a request without them gets a neutral row
             proc = ops.processor_rows(repetition_penalty, no_repeat_ngram_size, None, min_new_tokens, prompt_len=S,
                                       device=self.ll.device)
+        if (allowed_sequences is not None or forced_eos_at is not None) and self.constraints is None:
+            raise ValueError("add(allowed_sequences= / forced_eos_at=) needs ContinuousBatcher(..., constraints=True)")
+        if forced_eos_at is not None and (isinstance(forced_eos_at, bool) or not isinstance(forced_eos_at, int) or forced_eos_at < 1):
+            raise ValueError(f"forced_eos_at must be an int >= 1 (the new token that is forced to EOS), got {forced_eos_at!r}")
         free = self.free_slots()
         if not free:
             raise RuntimeError("no free slot")
         slot = free[0]
         if S + 1 > self.ctx_max:
             raise ValueError("prompt does not fit the slot")
+        con = None
+        if self.constraints is not None:                         # validates; the trie goes into the slot's own region
+            root = -1 if allowed_sequences is None else ops.constraint_trie(self.constraints, slot, allowed_sequences)
+            con = ops.constraint_rows(self.constraints, 1, begin=S, max_length=0 if forced_eos_at is None else S + forced_eos_at,
+                                      trie_root=root, device=self.ll.device)
         self.cache.key_valid[slot] = 1
         row = type(self.cache).rows_of(self.cache, slot, slot + 1)
         out = self.model(input_ids=ids, images=images, attention_mask=attention_mask, past_key_values=row, use_cache=True)
@@ -216,12 +246,17 @@ class ContinuousBatcher:
         scored = None
         if self.logprobs is not None:                            # the raw logits: before the processors and the draw rewrite them
             last = last.float().contiguous()
-            scored = score_raw(last, self.logprobs, proc is not None or params is not None)
+            scored = score_raw(last, self.logprobs, proc is not None or params is not None or con is not None)
         if proc is not None:                                     # the slot's history: the prompt; the first token is processed
             self.sess.proc[slot:slot + 1].copy_(proc)
             self.sess.hist[slot, :S] = ids[0].to(torch.int32)
             last = last.float().contiguous()
             ops.logits_process(last, proc, self.sess.hist[slot:slot + 1], None, S, None, self.sess.proc_eos)
+        if con is not None:                                      # behind the processors, on the same history
+            self.sess.con[slot:slot + 1].copy_(con)
+            self.sess.hist[slot, :S] = ids[0].to(torch.int32)
+            last = last.float().contiguous()
+            ops.constrain(last, con, self.constraints, self.sess.hist[slot:slot + 1], None, S)
         if first_token is not None:
             tok = int(first_token)
         elif params is not None and temperature >= ops.GREEDY_T:
@@ -294,6 +329,8 @@ class ContinuousBatcher:
             self.sess.check()                                    # once per leaving request (the step's D2H read has synchronised already)
         if self.spec_k is not None and self.live[slot]:
             self.sess.release(slot)
+        if self.constraints is not None:                         # the slot's row back to neutral: nothing carries over
+            self.sess.con[slot:slot + 1].copy_(ops.constraint_rows(self.constraints, 1, flags=0))
         self.live[slot] = False
 
     def speculation(self, slot: int) -> dict:

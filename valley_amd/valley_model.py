@@ -647,7 +647,9 @@ class ValleyLlamaForCausalLM:
                  seed=None, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False,
                  num_return_sequences: int = 1, return_dict_in_generate: bool = False, repetition_penalty=None,
                  no_repeat_ngram_size=None, min_length=None, min_new_tokens=None, output_logprobs: bool = False,
-                 top_logprobs: int = 0, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, prefix=None, **kw):
+                 top_logprobs: int = 0, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, prefix=None,
+                 bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, forced_eos_token_id=None,
+                 allowed_sequences=None, **kw):
         """Prefill + per-token KV decode (the loop of serve/model_worker.py:371-394; the reference's CLI
         path reaches the same through HF ``generate``, valley_model.py:432).  Greedy when not sampling or
         temperature < 1e-4, else temperature softmax + multinomial.  Decode steps run through a
@@ -669,6 +671,18 @@ class ValleyLlamaForCausalLM:
         step too; the minimum lengths need ``eos_token_id``.  Greedy and sampling take them for any row count; beam search
         takes them within its own limit (the KV reorder moves at most 128 rows of 16-bit or 64 rows of fp32 cache).  Left at
         their defaults, nothing changes.
+
+        ``bad_words_ids``, ``suppress_tokens``, ``begin_suppress_tokens`` and ``forced_eos_token_id`` are HF's token constraints
+        (NoBadWords, SuppressTokens, SuppressTokensAtBegin, ForcedEOSToken), behind the processors above in HF's order;
+        ``allowed_sequences`` — token-id lists shared by all rows, or one list of them per row — is the closed answer set HF
+        can only express as a ``prefix_allowed_tokens_fn`` callback: every row generates exactly one of its sequences, then
+        EOS.  All five run on the device (ops.constrain, one launch behind ops.logits_process), inside the captured step too,
+        in every route, for any row count, greedy or sampling, with the processors, ``output_logprobs`` (which stay those of
+        the raw logits), ``prefix=`` and the quantized engines.  A bad word or an allowed sequence holds at most 64 tokens;
+        ``allowed_sequences`` and ``forced_eos_token_id`` need ``eos_token_id`` (the forced ids are those ids), ids must lie
+        in the vocabulary.  Beam search takes the first three; ``prompt_lookup_num_tokens`` none.  Left at None, nothing
+        changes and nothing more is launched.  (``prefix_allowed_tokens_fn`` itself, ``sequence_bias`` and grammars are not
+        provided.)
 
         ``output_logprobs`` (with ``return_dict_in_generate``): the result gains ``token_logprobs`` fp32 [B, new tokens] =
         log_softmax(raw model logits)[token] — before the processors, the temperature and top-k / top-p; HF's
@@ -702,6 +716,11 @@ class ValleyLlamaForCausalLM:
             prefix.refuse(input_ids, attention_mask, self.model.precision, "generate(prefix=)")
             if prefix.model is not self:
                 raise ValueError("generate(prefix=): the session belongs to another model")
+        con = (bad_words_ids, suppress_tokens, begin_suppress_tokens, forced_eos_token_id, allowed_sequences)
+        if prompt_lookup_num_tokens is not None and any(a is not None for a in con):
+            raise ValueError("prompt_lookup_num_tokens is not supported with token constraints (bad_words_ids, suppress_tokens, "
+                             "begin_suppress_tokens, forced_eos_token_id, allowed_sequences): they rewrite the logits a draft is "
+                             "checked against")
         spec = self._spec_args(prompt_lookup_num_tokens, max_matching_ngram_size, input_ids, do_sample, num_beams, repetition_penalty,
                                no_repeat_ngram_size, min_length, min_new_tokens, output_logprobs or top_logprobs, use_graph, seed)
         proc = (repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens)
@@ -724,7 +743,7 @@ class ValleyLlamaForCausalLM:
                 raise ValueError(f"num_return_sequences ({num_return_sequences}) must be <= num_beams ({num_beams})")
             seq, scores = generation._generate_beams(self, input_ids, images, attention_mask, max_new_tokens, int(num_beams), length_penalty,
                                                      early_stopping, int(num_return_sequences), stopping_criteria, eos_token_id, use_graph,
-                                                     kw.get("pad_token_id", getattr(self.config, "pad_token_id", None)), proc)
+                                                     kw.get("pad_token_id", getattr(self.config, "pad_token_id", None)), proc, con=con)
             return SimpleNamespace(sequences=seq, sequences_scores=scores) if return_dict_in_generate else seq
         if num_return_sequences != 1:
             raise ValueError("num_return_sequences > 1 needs num_beams > 1 (sampling several sequences per prompt is not supported)")
@@ -736,7 +755,7 @@ class ValleyLlamaForCausalLM:
         seq, lp_out = generation._generate(self, input_ids, images, attention_mask, max_new_tokens, do_sample, temperature, stopping_criteria,
                                            eos_token_id, use_graph, top_k, top_p, seed,
                                            kw.get("pad_token_id", getattr(self.config, "pad_token_id", None)), proc=proc,
-                                           logprobs=top_logprobs if output_logprobs else None, prefix=prefix)
+                                           logprobs=top_logprobs if output_logprobs else None, prefix=prefix, con=con)
         return SimpleNamespace(sequences=seq, sequences_scores=None, **lp_out) if return_dict_in_generate else seq
 
     def _spec_args(self, k, max_ngram, input_ids, do_sample, num_beams, rp, nr, ml, mn, logprobs, use_graph, seed=None):
@@ -865,7 +884,9 @@ class ValleyLlamaForCausalLM:
                                                             "length_penalty", "early_stopping", "repetition_penalty",
                                                             "no_repeat_ngram_size", "min_length", "min_new_tokens",
                                                             "output_logprobs", "top_logprobs", "prompt_lookup_num_tokens",
-                                                            "max_matching_ngram_size", "seed", "prefix")}
+                                                            "max_matching_ngram_size", "seed", "prefix", "bad_words_ids",
+                                                            "suppress_tokens", "begin_suppress_tokens", "forced_eos_token_id",
+                                                            "allowed_sequences")}
         self.last_generation = None
         if gk.get("output_logprobs"):                        # the log-probabilities of the answer: kept on ``last_generation``
             self.last_generation = self.generate(input_ids=input_ids, images=images, stopping_criteria=[stopping],
