@@ -31,6 +31,7 @@ LIB_SPEC_SAMPLE = os.path.join(LIBDIR, "libvalley_hip_spec_sample.so")     # the
 LIB_SPEC_ROWS = os.path.join(LIBDIR, "libvalley_hip_spec_rows.so")         # the verify step of several sequences, one position each
 LIB_SUFFIX = os.path.join(LIBDIR, "libvalley_hip_suffix.so")               # split attention of 1..64 new queries over a cached prefix
 LIB_CONSTRAIN = os.path.join(LIBDIR, "libvalley_hip_constrain.so")         # token constraints: bad words, suppressed ids, forced EOS, tries
+LIB_GUIDE = os.path.join(LIBDIR, "libvalley_hip_guide.so")                 # classifier-free guidance: the two rows' combine, the token follow
 # the C prologue every companion compiles (error text, launch check, the version / last-error entry points)
 COMPANION_SHARED = ["companion_capi.hpp"]
 
@@ -70,6 +71,12 @@ COMPANIONS_CONSTRAIN = (
     Companion("constrain", LIB_CONSTRAIN, ("constrain.hip",), "valley_hip_constrain.h", ()),
 )
 ALL_COMPANIONS = (*COMPANIONS, *COMPANIONS_ROWS, *COMPANIONS_SUFFIX, *COMPANIONS_CONSTRAIN)
+# classifier-free guidance: a fifth table, walked by the same code.  The four above and their sum are what the other libraries'
+# tests count, so the sum keeps its four tables and the build walks EVERY_COMPANION
+COMPANIONS_GUIDE = (
+    Companion("guide", LIB_GUIDE, ("guide.hip",), "valley_hip_guide.h", ("beam_rows.inc",)),
+)
+EVERY_COMPANION = (*ALL_COMPANIONS, *COMPANIONS_GUIDE)
 SOURCES = ["capi.hip", "gemm_bf16.hip", "gemm_p32.hip", "gemm_p16.hip", "gemm_streamk.hip", "norm_elementwise.hip", "attention.hip", "temporal_delta.hip", "preprocess.hip", "gemv_bf16.hip", "precise_f32.hip", "gemm_skinny.hip", "decode_step.hip", "sampling.hip"]
 
 
@@ -85,8 +92,8 @@ def hipcc() -> str:
 
 def needs_build() -> bool:
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h)
-                                                                 for h in ("valley_hip.h", *(c.header for c in ALL_COMPANIONS))]
-    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, *(c.lib for c in ALL_COMPANIONS)):
+                                                                 for h in ("valley_hip.h", *(c.header for c in EVERY_COMPANION))]
+    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, *(c.lib for c in EVERY_COMPANION)):
         if not os.path.exists(lib):
             return True
         t = os.path.getmtime(lib)
@@ -98,7 +105,7 @@ def needs_build() -> bool:
 def build(force: bool = False, verbose: bool = True) -> str:
     """The two shipped libraries (bf16 and fp16 storage) and the experimental one, every stale translation unit compiled in parallel."""
     os.makedirs(LIBDIR, exist_ok=True)
-    for sub in ("f16", "exp", "exp_f16", *(c.name for c in ALL_COMPANIONS)):
+    for sub in ("f16", "exp", "exp_f16", *(c.name for c in EVERY_COMPANION)):
         os.makedirs(os.path.join(LIBDIR, sub), exist_ok=True)
     if not force and not needs_build():
         return LIB
@@ -127,7 +134,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
             jobs.append((s, cmd))
             if s in AUDITED:
                 audits.append((s, odir, " ".join(flags) or "(default flags)"))
-    for c in ALL_COMPANIONS:
+    for c in EVERY_COMPANION:
         cdir = os.path.join(LIBDIR, c.name)
         for s in c.sources:
             o = os.path.join(cdir, s.replace(".hip", ".o"))
@@ -177,7 +184,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
-    for c in ALL_COMPANIONS:
+    for c in EVERY_COMPANION:
         cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", c.lib] + \
             [os.path.join(LIBDIR, c.name, s.replace(".hip", ".o")) for s in c.sources]
         if verbose:

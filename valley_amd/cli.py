@@ -132,9 +132,24 @@ def main(args) -> str:
     gen = dict(SAMPLED if sampled else GREEDY)
     # HF's prompt_lookup_num_tokens: same answer, fewer decode steps (sampled: the same answer as the same seed without it)
     gen.update(lookup_kwargs(getattr(args, "prompt_lookup", None), getattr(args, "seed", None), sampled))
+    gen.update(guidance_kwargs(tokenizer, getattr(args, "guidance_scale", None), getattr(args, "negative_prompt", None)))
     answer = model.completion(tokenizer, args.video_file, turns, gen, _require_gpu())
     print(answer)
     return answer
+
+
+def guidance_kwargs(tokenizer, guidance_scale=None, negative_prompt=None) -> dict:
+    """The ``generate`` arguments of ``--guidance-scale G`` / ``--negative-prompt TEXT``: nothing without the scale.  The negative
+    prompt is plain text (no frames: the unconditional row is the language prior); without one HF's default applies, the prompt's
+    last token."""
+    if guidance_scale is None:
+        if negative_prompt is not None:
+            raise ValueError("--negative-prompt needs --guidance-scale")
+        return {}
+    kw = {"guidance_scale": float(guidance_scale)}
+    if negative_prompt is not None:
+        kw["negative_prompt_ids"] = torch.as_tensor(tokenizer([negative_prompt]).input_ids)
+    return kw
 
 
 def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
@@ -155,6 +170,11 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap.add_argument("--seed", type=int, default=None, metavar="N",
                     help="seed of the on-device draws of --sample; with --prompt-lookup a missing seed is drawn once and printed "
                          "to stderr")
+    ap.add_argument("--guidance-scale", type=float, default=None, metavar="G",
+                    help="classifier-free guidance (HF's guidance_scale): decode a second, unconditional row and push the answer "
+                         "away from it by G (1 = off)")
+    ap.add_argument("--negative-prompt", type=str, default=None, metavar="TEXT",
+                    help="the unconditional row's prompt, as text without frames (default: the prompt's last token, as in HF)")
     return ap.parse_args(argv)
 
 

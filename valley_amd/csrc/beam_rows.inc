@@ -70,16 +70,24 @@ BM_DEVICE float block_sum(float v, float* red) {
 // the log-sum-exp of a row: m + log(sum exp(x - m)) over its non-NaN values, 0 when the maximum is not finite.  visit_x(f)
 // calls f(i, x_i) for the thread's elements i = tid, tid + ROW_THREADS, ... in that order: with the fixed block reductions
 // the result has the same bits in every kernel that visits a row this way
+// (row_max: the row's maximum over its non-NaN values, -inf for a row without one, for a caller that needs it too)
 template <typename VisitX>
-BM_DEVICE float row_lse(VisitX&& visit_x, float* red) {
+BM_DEVICE float row_lse(VisitX&& visit_x, float* red, float& row_max) {
     float m = -INFINITY;
     visit_x([&](int, float v) { m = fmaxf(m, v); });            // (fmaxf ignores NaN)
     m = block_max(m, red);
+    row_max = m;
     float s = 0.f;
     if (m > -INFINITY && m < INFINITY)
         visit_x([&](int, float v) { if (v == v) s += expf(v - m); });
     s = block_sum(s, red);
     return (m > -INFINITY && m < INFINITY) ? m + logf(s) : 0.f;
+}
+
+template <typename VisitX>
+BM_DEVICE float row_lse(VisitX&& visit_x, float* red) {
+    float m;
+    return row_lse(visit_x, red, m);
 }
 
 template <bool REG, bool LSE>

@@ -68,7 +68,8 @@ def _gemv_residual(sess, a, L, name):
 class DecodeSession:
     def __init__(self, llama: HipLlama, cache: HipKVCache, use_graph: bool = True, per_row_positions: bool = False,
                  sampling: bool = False, beams: Optional[tuple] = None, processors: bool = False,
-                 processor_eos: Optional[Sequence[int]] = None, logprobs: Optional[int] = None, constraints=None):
+                 processor_eos: Optional[Sequence[int]] = None, logprobs: Optional[int] = None, constraints=None,
+                 guidance: bool = False):
         """``per_row_positions``: every batch row is an independent sequence at its own position (``pos`` is int32 [B]
         and advances by one per step for every row) — the captured step of valley_amd.serving.ContinuousBatcher.
         ``sampling``: the step draws each row's next token with that row's parameters in ``self.sample`` (int32 [B, 6],
@@ -99,7 +100,13 @@ class DecodeSession:
         forced EOS, allowed-sequence tries — run right behind the processors' launch (ops.constrain), before the argmax /
         draw / beam candidates, with each row's parameters in ``self.con`` (int32 [B, 4], ops.constraint_rows; all rows
         neutral until written).  It implies ``processors`` (that launch appends the fed token to the history the constraints
-        read; its rows stay neutral unless written).  Rows, table contents and counts are read at every replay."""
+        read; its rows stay neutral unless written).  Rows, table contents and counts are read at every replay.
+        ``guidance`` (per-row sessions only; not with beams or logprobs): classifier-free guidance over pairs of rows, each
+        pair's roles, scale and plausibility cut-off in ``self.guide`` (int32 [B, 4], ops.guidance_rows; all rows neutral until
+        written, read at every replay).  Right behind the lm_head a conditional row's logits are combined with its
+        unconditional partner's (ops.guide: HF puts this processor first), then the processors, the constraints and the
+        argmax / draw run as ever, and the unconditional row takes its conditional row's token (ops.guide_follow) before
+        pos += 1: both rows of a pair are fed the same token at the next step."""
         self.ll, self.cache = llama, cache
         B, d = cache.batch, llama.device
         if B > 8:
@@ -158,6 +165,14 @@ class DecodeSession:
             self.running = torch.zeros((B,), dtype=torch.float32, device=d)
             self.kv_table = None
             self._kv_table_gen = None
+        self.guide = None
+        if guidance:
+            if not per_row_positions:
+                raise ValueError("DecodeSession(guidance=True) needs per_row_positions=True (the two rows of a pair are sequences "
+                                 "of their own lengths)")
+            if beams is not None or logprobs is not None:
+                raise ValueError("DecodeSession(guidance=True) takes no beams and no logprobs")
+            self.guide = ops.guidance_rows(B, device=d)
         self.proc = self.hist = self.proc_eos = None
         self.con, self.con_tables = None, constraints
         if constraints is not None:
@@ -240,6 +255,8 @@ class DecodeSession:
             if tail:
                 self.beam_tail()
             return
+        if self.guide is not None:                   # first, as in HF: every processor behind sees the guided scores
+            ops.guide(self.logits[:, :ll.V], self.guide)
         if self.lp_n is not None:                    # lse (and the top-n) of the raw logits, before anything rewrites them
             ops.token_logprobs(self.logits[:, :ll.V], top=self.lp_n, out_lse=self.lp_lse, copy=self.lp_raw, out_top=self.lp_top)
         if self.proc is not None:                    # the token fed to this step joins the history at index pos
@@ -252,6 +269,8 @@ class DecodeSession:
             ops.argmax(self.logits[:, :ll.V], sampling=self.sample, ctr=self.pos, ctr_add=1, out=self.tok)
         if self.lp_n is not None:                    # the token just chosen has index pos + 1 in its row's sequence
             self._record(1)
+        if self.guide is not None:                   # the unconditional row is fed its conditional row's token
+            ops.guide_follow(self.tok, self.guide)
         ops.incr_i32(self.pos, 1)
 
     def _record(self, len_add: int):

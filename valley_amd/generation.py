@@ -193,6 +193,37 @@ def _generate_spec(model, input_ids, images, attention_mask, max_new_tokens, sto
     return seq, speculation
 
 
+def token_loop(step, token, seq, finished, eos, stopping_criteria, max_new_tokens, cache, d):
+    """The loop of ``_generate`` and ``_generate_guided`` behind the first token: a row has finished once it emitted an EOS id or a
+    stopping criterion fired on the sequences so far (``finished`` is updated in place; ``step`` pads a finished row's tokens); the
+    loop ends when every row has, at ``max_new_tokens`` or with the cache full.  -> the sequences."""
+    for _ in range(max_new_tokens - 1):
+        if eos is not None:
+            finished |= torch.isin(token, eos)
+        for a in criterion_answers(stopping_criteria, seq, d, d):
+            finished |= a if isinstance(a, torch.Tensor) else torch.full_like(finished, a)
+        if bool(finished.all()) or cache.seq_len + 1 > cache.ctx_max:
+            break
+        token = step(token)
+        seq = torch.cat([seq, token[:, None]], dim=1)
+    return seq
+
+
+def sampling_setup(do_sample, temperature, top_k, top_p, seed, B, device):
+    """(greedy, per-row parameters of the on-device draw or None): sampling with any of top_k / top_p / seed draws on the device,
+    row r with seed + r (or its own seed of a list); without a seed one is drawn from torch's generator."""
+    greedy = not (do_sample and temperature >= ops.GREEDY_T)
+    sample = None
+    if not greedy and (top_k is not None or top_p is not None or seed is not None):
+        if seed is None:
+            seed = int(torch.randint(0, 1 << 62, (1,)).item())           # reproducible under torch.manual_seed
+        seeds = [(int(seed) + r) % (1 << 64) for r in range(B)] if not isinstance(seed, (list, tuple)) else list(seed)
+        if len(seeds) != B:
+            raise ValueError(f"generate: {len(seeds)} seeds for {B} rows")
+        sample = ops.sampling_rows(float(temperature), 0 if top_k is None else top_k, 1.0 if top_p is None else top_p, seeds, device=device)
+    return greedy, sample
+
+
 def _generate(model, input_ids, images, attention_mask, max_new_tokens, do_sample, temperature, stopping_criteria, eos_token_id,
               use_graph, top_k, top_p, seed, pad, proc=None, logprobs=None, prefix=None, con=None):
     """Greedy decoding and sampling: the first token from the prefill's logits, then one ``step`` per token (the decode session's, or
@@ -202,15 +233,7 @@ def _generate(model, input_ids, images, attention_mask, max_new_tokens, do_sampl
     B, S = input_ids.shape
     con = constraint_setup(con, model.model.llama.V, S, max_new_tokens, eos_ids(eos_token_id), d, B)
     cache, out = _prefill(model, prefix, input_ids, images, attention_mask, B, S, max_new_tokens)
-    greedy = not (do_sample and temperature >= ops.GREEDY_T)
-    sample = None                                            # per-row parameters of the on-device draw
-    if not greedy and (top_k is not None or top_p is not None or seed is not None):
-        if seed is None:
-            seed = int(torch.randint(0, 1 << 62, (1,)).item())           # reproducible under torch.manual_seed
-        seeds = [(int(seed) + r) % (1 << 64) for r in range(B)] if not isinstance(seed, (list, tuple)) else list(seed)
-        if len(seeds) != B:
-            raise ValueError(f"generate: {len(seeds)} seeds for {B} rows")
-        sample = ops.sampling_rows(float(temperature), 0 if top_k is None else top_k, 1.0 if top_p is None else top_p, seeds, device=d)
+    greedy, sample = sampling_setup(do_sample, temperature, top_k, top_p, seed, B, d)
     on_device = greedy or sample is not None                 # else the host draws: torch.multinomial over the step's logits
 
     def pick(last, ctr):                                     # ctr: index of the drawn token in the sequence
@@ -295,15 +318,7 @@ def _generate(model, input_ids, images, attention_mask, max_new_tokens, do_sampl
         return token
 
     step = forward_step if sess is None else session_step
-    for _ in range(max_new_tokens - 1):
-        if eos is not None:
-            finished |= torch.isin(token, eos)
-        for a in criterion_answers(stopping_criteria, seq, d, d):
-            finished |= a if isinstance(a, torch.Tensor) else torch.full_like(finished, a)
-        if bool(finished.all()) or cache.seq_len + 1 > cache.ctx_max:
-            break
-        token = step(token)
-        seq = torch.cat([seq, token[:, None]], dim=1)
+    seq = token_loop(step, token, seq, finished, eos, stopping_criteria, max_new_tokens, cache, d)
     finish(d, sess)
     lp_out = {}
     if logprobs is not None:                                 # one read of the session's tables, after the loop
@@ -319,6 +334,161 @@ def _generate(model, input_ids, images, attention_mask, max_new_tokens, do_sampl
     if prefix is not None:
         prefix.settle(seq)
     return seq, lp_out
+
+
+GUIDANCE_KEYS = ("guidance_scale", "negative_prompt_ids", "negative_prompt_attention_mask", "negative_images", "guidance_plausibility")
+GUIDANCE_MAX_ROWS = 4                                        # prompts of a guided generation: 2 rows each in the 8-row decode step
+
+
+def guidance_scalars(scale, beta):
+    """A request's ``guidance_scale`` and ``guidance_plausibility``, checked -> (float scale, float beta), or None where guidance
+    is off (a scale of None or 1, as in HF)."""
+    import math
+    if scale is None:
+        if beta not in (None, 0, 0.0):
+            raise ValueError("guidance_plausibility needs a guidance_scale")
+        return None
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(scale):
+        raise ValueError(f"guidance_scale must be a finite float, got {scale!r}")
+    beta = 0.0 if beta is None else beta
+    if isinstance(beta, bool) or not isinstance(beta, (int, float)) or not 0.0 <= beta <= 1.0:
+        raise ValueError(f"guidance_plausibility must lie in [0, 1], got {beta!r}")
+    return None if scale == 1 else (float(scale), float(beta))
+
+
+def negative_prompt(input_ids, neg_ids, neg_mask, device):
+    """HF's unconditional context: the negative prompt [B, S_neg] and its mask, or — without one — each row's last prompt token."""
+    B = input_ids.shape[0]
+    if neg_ids is None:
+        if neg_mask is not None:
+            raise ValueError("negative_prompt_attention_mask needs negative_prompt_ids")
+        return input_ids[:, -1:].to(device), None
+    neg_ids = torch.as_tensor(neg_ids)
+    if neg_ids.dim() != 2 or neg_ids.shape[0] != B or neg_ids.shape[1] < 1:
+        raise ValueError(f"negative_prompt_ids must be [{B}, S_neg] (one negative prompt per prompt row), got {tuple(neg_ids.shape)}")
+    if neg_mask is not None:
+        neg_mask = torch.as_tensor(neg_mask)
+        if tuple(neg_mask.shape) != tuple(neg_ids.shape):
+            raise ValueError(f"negative_prompt_attention_mask must have negative_prompt_ids' shape {tuple(neg_ids.shape)}, got "
+                             f"{tuple(neg_mask.shape)}")
+    return neg_ids.to(device), neg_mask
+
+
+def guidance_args(model, input_ids, guidance_scale, negative_prompt_ids, negative_prompt_attention_mask, negative_images,
+                  guidance_plausibility, num_beams, prompt_lookup_num_tokens, prefix, output_logprobs, use_graph):
+    """``generate``'s guidance arguments checked -> (scale, beta, negative ids, negative mask, negative images), or None where
+    guidance is off; every combination the guided loop does not cover is refused here, before the model is touched."""
+    if guidance_scale is None and any(a is not None for a in (negative_prompt_ids, negative_prompt_attention_mask, negative_images)):
+        raise ValueError("negative_prompt_ids / negative_prompt_attention_mask / negative_images need a guidance_scale")
+    g = guidance_scalars(guidance_scale, guidance_plausibility)
+    if g is None:
+        return None
+    if input_ids.dim() != 2 or input_ids.shape[0] > GUIDANCE_MAX_ROWS:
+        raise ValueError(f"guidance_scale decodes two rows per prompt in the 8-row decode step: at most {GUIDANCE_MAX_ROWS} prompt "
+                         f"rows, got input_ids {tuple(input_ids.shape)}")
+    if num_beams is not None and not isinstance(num_beams, bool) and int(num_beams) > 1:
+        raise ValueError("guidance_scale is not supported with num_beams > 1")
+    if prompt_lookup_num_tokens is not None:
+        raise ValueError("guidance_scale is not supported with prompt_lookup_num_tokens (guidance rewrites the logits a draft is "
+                         "checked against)")
+    if prefix is not None:
+        raise ValueError("guidance_scale is not supported with prefix= (a session holds one row)")
+    if output_logprobs:
+        raise ValueError("guidance_scale is not supported with output_logprobs")
+    if use_graph is None:
+        raise ValueError("guidance_scale needs the decode session: use_graph True (captured) or False (eager), not None")
+    if model.model.precision == "fp32":
+        raise ValueError("guidance_scale needs a 16-bit or weight-quantized engine (the decode session's), not fp32")
+    neg_ids, neg_mask = negative_prompt(input_ids, negative_prompt_ids, negative_prompt_attention_mask, model.device)
+    return g[0], g[1], neg_ids, neg_mask, negative_images
+
+
+def _generate_guided(model, input_ids, images, attention_mask, max_new_tokens, do_sample, temperature, stopping_criteria, eos_token_id,
+                     use_graph, top_k, top_p, seed, pad, guide, proc=None, con=None):
+    """Classifier-free guidance (HF's ``guidance_scale`` / ``negative_prompt_ids``; ``guide`` = guidance_args'): the B prompts and
+    their B negative prompts are prefilled into rows [0, B) and [B, 2B) of one cache and decoded by one per-row session of 2B rows
+    (DecodeSession ``guidance``).  Row b's logits become scale * (lc - lu) + lu of its own and row B + b's log-softmax
+    (ops.guide) in front of the processors, the constraints and the draw, which act on the conditional rows as in ``_generate``;
+    row B + b is then fed row b's token (ops.guide_follow).  Stop rule, padding and the end are ``_generate``'s."""
+    from .decode import DecodeSession
+    scale, beta, neg_ids, neg_mask, neg_images = guide
+    d, ll = model.device, model.model.llama
+    input_ids = input_ids.to(d)
+    B, S = input_ids.shape
+    Sn, R = neg_ids.shape[1], 2 * B
+    eos_list = eos_ids(eos_token_id) or None
+    con = constraint_setup(con, ll.V, S, max_new_tokens, eos_list or [], d, B)
+    table = processor_table(proc, S, eos_list, d, B)
+    rows = ops.guidance_rows(R, [(b, B + b, scale, beta) for b in range(B)], device=d)
+    top = max(S, Sn)
+    cache = ll.new_cache(R, max(context_limit(model.config, top, max_new_tokens), top + 1))
+    cache.key_valid = torch.ones((R, cache.ctx_max), dtype=torch.uint8, device=d)
+    half = type(cache).rows_of
+    out_c = model.forward(input_ids=input_ids, images=images, attention_mask=attention_mask, past_key_values=half(cache, 0, B), use_cache=True)
+    out_u = model.forward(input_ids=neg_ids, images=neg_images, attention_mask=neg_mask, past_key_values=half(cache, B, R), use_cache=True)
+    cache.seq_len = top                                      # the deeper half: what the loop's room test counts
+    greedy, sample = sampling_setup(do_sample, temperature, top_k, top_p, seed, B, d)
+    if sample is not None:                                   # the unconditional rows take the argmax of their own logits, then follow
+        sample = torch.cat([sample, ops.sampling_rows([0.0] * B, device=d)])
+    on_device = greedy or sample is not None
+
+    eos = None if eos_list is None else torch.as_tensor(eos_list, device=d)
+    if pad is None:
+        pad = int(eos[0]) if eos is not None else 0
+    finished = torch.zeros((B,), dtype=torch.bool, device=d)
+    if con is not None and table is None:                    # the constraints read the history the processors' launch appends to
+        table = ops.processor_rows([None] * B, device=d)
+    eos32 = hist = None
+    if table is not None:                                    # the conditional rows' whole input_ids, as in HF; the others stay neutral
+        table = torch.cat([table, ops.processor_rows([None] * B, device=d)])
+        eos32 = None if eos is None else eos.to(torch.int32)
+        hist = torch.zeros((R, cache.ctx_max), dtype=torch.int32, device=d)
+        hist[:B, :S] = input_ids.to(torch.int32)
+        hist[B:, :Sn] = neg_ids.to(torch.int32)
+    con_rows = None if con is None else torch.cat([con[1], ops.constraint_rows(con[0], B, flags=0, device=d)])
+    pos = torch.tensor([S] * B + [Sn] * B, dtype=torch.int32, device=d)
+
+    last = torch.cat([out_c.logits[:, -1, :], out_u.logits[:, -1, :]]).float().contiguous()
+    ops.guide(last, rows)                                    # the first token: the same launch on the two prefills' last logits
+    if table is not None:
+        ops.logits_process(last, table, hist, pos, 0, None, eos32)
+        if con is not None:
+            ops.constrain(last, con_rows, con[0], hist, pos, 0)
+
+    def pick(x, ctr_add):                                    # x [2B, V] -> the conditional rows' tokens [B]
+        if on_device:
+            tok = ops.argmax(x) if sample is None else ops.argmax(x, sampling=sample, ctr=pos, ctr_add=ctr_add)
+            return tok[:B].to(torch.long)
+        return torch.multinomial(torch.softmax(x[:B] / temperature, dim=-1), num_samples=1).view(B)
+
+    token = pick(last, 0)
+    seq = torch.cat([input_ids, token[:, None]], dim=1)
+    sess = DecodeSession(ll, cache, use_graph=bool(use_graph), per_row_positions=True, sampling=sample is not None,
+                         processors=table is not None, processor_eos=eos_list, guidance=True,
+                         **({} if con is None else {"constraints": con[0]}))
+    sess.guide.copy_(rows)
+    if sample is not None:
+        sess.sample.copy_(sample)
+    if table is not None:
+        sess.proc.copy_(table)
+        sess.hist.copy_(hist)
+    if con is not None:
+        sess.con.copy_(con_rows)
+    sess.pos.copy_(pos)
+    sess.tok.copy_(token.to(torch.int32).repeat(2))
+    sess.begin()
+
+    def step(token):
+        nxt = sess.step()
+        token = nxt[:B].to(torch.long).clone() if on_device else pick(sess.logits[:, :ll.V], None)
+        if bool(finished.any()) or not on_device:
+            token = torch.where(finished, torch.full_like(token, pad), token)
+            sess.tok.copy_(token.to(torch.int32).repeat(2))
+        return token
+
+    seq = token_loop(step, token, seq, finished, eos, stopping_criteria, max_new_tokens, cache, d)
+    finish(d, sess)
+    return seq
 
 
 def _generate_beams(model, input_ids, images, attention_mask, max_new_tokens, nb, length_penalty, early_stopping, nrs,

@@ -1745,6 +1745,74 @@ def constrain(logits: torch.Tensor, rows: torch.Tensor, tables: ConstraintTables
     return logits
 
 
+# ---- classifier-free guidance (libvalley_hip_guide.so, include/valley_hip_guide.h) -------------------------------------------
+GUIDE_NEUTRAL, GUIDE_COND, GUIDE_UNCOND = 0, 1, 2      # VLY_GUIDE_<role>
+
+
+def guidance_rows(R: int, pairs=(), device=None) -> torch.Tensor:
+    """Per-row parameters of ``guide`` / ``guide_follow`` as int32 [R, 4]: {role, partner, scale (fp32 bits), log(beta) (fp32
+    bits)}.  ``pairs``: (cond_row, uncond_row, scale, plausibility) each — the conditional row's logits become
+    scale * (lc - lu) + lu over the two rows' log-softmaxes, and with a plausibility beta in (0, 1] every token whose conditional
+    probability is below beta times the most probable one's is banned (beta = 0: no cut-off, stored as -inf).  Rows no pair
+    names are neutral: ``guidance_rows(R)`` is a neutral table."""
+    import math
+    if isinstance(R, bool) or not isinstance(R, int) or R < 1:
+        raise ValueError(f"guidance_rows: R must be an int >= 1, got {R!r}")
+    t = torch.zeros((R, 4), dtype=torch.int32)
+    t[:, 1] = -1
+    f = t.view(torch.float32)
+    f[:, 2], f[:, 3] = 1.0, float("-inf")
+    used = set()
+    for p in pairs:
+        if not isinstance(p, (list, tuple)) or len(p) != 4:
+            raise ValueError(f"guidance_rows: a pair is (cond_row, uncond_row, scale, plausibility), got {p!r}")
+        c, u, scale, beta = p
+        for name, v in (("cond_row", c), ("uncond_row", u)):
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < R:
+                raise ValueError(f"guidance_rows: {name} must be an int in [0, {R}), got {v!r}")
+        if c == u or c in used or u in used:
+            raise ValueError(f"guidance_rows: the rows of all pairs must be distinct, got ({c}, {u}) behind {sorted(used)}")
+        if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(scale):
+            raise ValueError(f"guidance_rows: the scale must be a finite float, got {scale!r}")
+        if isinstance(beta, bool) or not isinstance(beta, (int, float)) or not 0.0 <= beta <= 1.0:
+            raise ValueError(f"guidance_rows: the plausibility must lie in [0, 1], got {beta!r}")
+        used.update((c, u))
+        t[c, 0], t[c, 1], t[u, 0], t[u, 1] = GUIDE_COND, u, GUIDE_UNCOND, c
+        f[c, 2] = float(scale)
+        f[c, 3] = math.log(beta) if beta > 0 else float("-inf")      # (the double's logarithm, rounded to fp32 by the store)
+    return t.to(device) if device is not None else t
+
+
+def guide(logits: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
+    """In place on logits fp32 [R, V] (row stride may exceed V): every conditional row of ``rows`` (int32 [R, 4],
+    ``guidance_rows``) becomes scale * (lc - lu) + lu of its own and its unconditional partner's log-softmax, behind its
+    plausibility cut-off; every other row keeps its bits.  In front of ``logits_process`` (HF puts the processor first).
+    Everything is read on the device."""
+    from . import lib_guide
+    _chk(logits, torch.float32, "logits", contiguous=False)
+    _chk(rows, torch.int32, "rows")
+    if logits.dim() != 2 or logits.stride(1) != 1 or tuple(rows.shape) != (logits.shape[0], 4):
+        raise ValueError(f"guide: logits [R, V] with unit column stride and rows [R, 4] expected, got {tuple(logits.shape)} / "
+                         f"{tuple(rows.shape)}")
+    R, V = logits.shape
+    rc = lib_guide.load().vly_guide_apply(logits.data_ptr(), logits.stride(0), V, R, rows.data_ptr(), _stream())
+    lib_guide.check(rc, "vly_guide_apply")
+    return logits
+
+
+def guide_follow(tok: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
+    """In place on tok int32 [R], behind the argmax / draw: every unconditional row of ``rows`` takes its conditional row's
+    token, so both rows of a pair are fed the same token at the next step."""
+    from . import lib_guide
+    _chk(tok, torch.int32, "tok")
+    _chk(rows, torch.int32, "rows")
+    if tok.dim() != 1 or tuple(rows.shape) != (tok.numel(), 4):
+        raise ValueError(f"guide_follow: tok [R] and rows [R, 4] expected, got {tuple(tok.shape)} / {tuple(rows.shape)}")
+    rc = lib_guide.load().vly_guide_follow(tok.data_ptr(), tok.numel(), rows.data_ptr(), _stream())
+    lib_guide.check(rc, "vly_guide_follow")
+    return tok
+
+
 # ---- token log-probabilities and the forward-only loss (libvalley_hip_score.so, include/valley_hip_score.h) ----------------
 SCORE_MAX_TOP = 20       # VLY_SCORE_MAX_TOP
 SCORE_MAX_V = 1 << 18

@@ -17,7 +17,7 @@ import torch
 
 from . import ops
 from .decode import DecodeSession
-from .generation import eos_ids, lookup_args, score_raw
+from .generation import eos_ids, guidance_scalars, lookup_args, negative_prompt, score_raw
 from .valley_model import (DEFAULT_IM_END_TOKEN, DEFAULT_IM_START_TOKEN, DEFAULT_IMAGE_PATCH_TOKEN, DEFAULT_VI_END_TOKEN,
                            DEFAULT_VI_START_TOKEN, DEFAULT_VIDEO_FRAME_TOKEN, DEFAULT_VIDEO_TOKEN)
 
@@ -114,7 +114,7 @@ class ContinuousBatcher:
                  processors: bool = False, eos_token_id=None, logprobs: Optional[int] = None,
                  prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None,
                  constraints: bool = False, bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None,
-                 trie_capacity: int = 4096):
+                 trie_capacity: int = 4096, guidance: bool = False):
         """``sampling``: the captured step draws every slot's token with the parameters ``add`` gave its request
         (temperature, top-k, top-p, seed; DecodeSession ``sampling``) — a seeded request's tokens then depend on its seed
         alone, not on its slot or its neighbours.  Greedy requests take the argmax in either kind of batcher.
@@ -139,9 +139,15 @@ class ContinuousBatcher:
         its own ``allowed_sequences`` — written into the slot's region of ``trie_capacity`` int32 words (2 per trie node + 2 per
         edge) between steps, without a re-capture — and its forced EOS.  ``eos_token_id`` is what ends an allowed sequence and
         what the forced EOS leaves.  A request's tokens do not depend on its slot or its neighbours.  Not with
-        ``prompt_lookup_num_tokens``."""
+        ``prompt_lookup_num_tokens``.
+        ``guidance``: the captured step runs classifier-free guidance (DecodeSession ``guidance``; ops.guide / ops.guide_follow).
+        A request ``add``ed with a ``guidance_scale`` takes TWO slots — its own and an unconditional one behind its negative
+        prompt — written into the step's table between steps, without a re-capture; every other request takes one, as ever.
+        Not with ``prompt_lookup_num_tokens`` or ``logprobs``."""
         if not 1 <= slots <= 8:
             raise ValueError("1 <= slots <= 8 (the decode step streams weights with the GEMV kernels)")
+        if guidance and (prompt_lookup_num_tokens is not None or logprobs is not None):
+            raise ValueError("guidance=True does not combine with prompt_lookup_num_tokens or logprobs")
         self.spec_k = None
         k, n = lookup_args(prompt_lookup_num_tokens, max_matching_ngram_size)
         if k is not None:
@@ -182,7 +188,11 @@ class ContinuousBatcher:
         else:
             self.sess = DecodeSession(self.ll, self.cache, use_graph=use_graph, per_row_positions=True, sampling=sampling,
                                       processors=processors, processor_eos=eos, **({} if logprobs is None else {"logprobs": logprobs}),
-                                      **({} if self.constraints is None else {"constraints": self.constraints}))
+                                      **({} if self.constraints is None else {"constraints": self.constraints}),
+                                      **({"guidance": True} if guidance else {}))
+        self.guidance = bool(guidance)
+        self.partner = [None] * slots                            # a guided request's other slot, in both directions
+        self.uncond = [False] * slots                            # the slot is the unconditional one of its pair
         self.logprobs = None if logprobs is None else int(logprobs)
         self.first_logprobs, self.last_logprobs = {}, {}
         self.live = [False] * slots
@@ -194,7 +204,8 @@ class ContinuousBatcher:
 
     def add(self, input_ids, images=None, attention_mask=None, first_token: Optional[int] = None, temperature: float = 0.0,
             top_k: int = 0, top_p: float = 1.0, seed: Optional[int] = None, repetition_penalty=None, no_repeat_ngram_size=None,
-            min_new_tokens=None, allowed_sequences=None, forced_eos_at: Optional[int] = None) -> int:
+            min_new_tokens=None, allowed_sequences=None, forced_eos_at: Optional[int] = None, guidance_scale=None,
+            negative_prompt_ids=None, negative_prompt_attention_mask=None, negative_images=None, guidance_plausibility=0.0) -> int:
         """Prefill one request (input_ids [1, S]) into a free slot; returns the slot.  The first generated token is the
         prefill's argmax unless ``first_token`` is given.  ``temperature`` >= 1e-4 (a sampling batcher only) makes the
         request sample: its first token is drawn on the device from the prefill's logits (draw counter S), the following
@@ -203,7 +214,15 @@ class ContinuousBatcher:
         processors for this request, applied to the prefill's logits (its first token) and inside every step.
         ``allowed_sequences`` (token-id lists: the request answers with exactly one of them, then EOS) and ``forced_eos_at = n``
         (its n-th new token can only be an EOS id: HF's forced EOS at max_new_tokens = n) need a constraints batcher, whose
-        shared lists apply to every request."""
+        shared lists apply to every request.
+        ``guidance_scale`` (a guidance batcher only; None or 1: off) with ``negative_prompt_ids`` [1, S_neg] (None: the prompt's
+        last token), its mask, ``negative_images`` (the unconditional row's frames; None: text only) and
+        ``guidance_plausibility`` are ``generate``'s: the request takes two free slots and the conditional one is returned."""
+        guide = guidance_scalars(guidance_scale, guidance_plausibility)
+        if guidance_scale is None and any(a is not None for a in (negative_prompt_ids, negative_prompt_attention_mask, negative_images)):
+            raise ValueError("negative_prompt_ids / negative_prompt_attention_mask / negative_images need a guidance_scale")
+        if guidance_scale is not None and not self.guidance:
+            raise ValueError("add(guidance_scale=) needs ContinuousBatcher(..., guidance=True)")
         if temperature > 0 and not self.sampling:
             raise ValueError("add(temperature > 0) needs ContinuousBatcher(..., sampling=True)")
         params = None
@@ -234,6 +253,12 @@ class ContinuousBatcher:
         slot = free[0]
         if S + 1 > self.ctx_max:
             raise ValueError("prompt does not fit the slot")
+        if guide is not None:                                    # validates; the second slot and the negative prompt
+            neg_ids, neg_mask = negative_prompt(ids, negative_prompt_ids, negative_prompt_attention_mask, self.ll.device)
+            if len(free) < 2:
+                raise RuntimeError("no two free slots for a guided request")
+            if neg_ids.shape[1] + 1 > self.ctx_max:
+                raise ValueError("negative prompt does not fit the slot")
         con = None
         if self.constraints is not None:                         # validates; the trie goes into the slot's own region
             root = -1 if allowed_sequences is None else ops.constraint_trie(self.constraints, slot, allowed_sequences)
@@ -243,6 +268,14 @@ class ContinuousBatcher:
         row = type(self.cache).rows_of(self.cache, slot, slot + 1)
         out = self.model(input_ids=ids, images=images, attention_mask=attention_mask, past_key_values=row, use_cache=True)
         last = out.logits[0, -1:]
+        if guide is not None:                                    # the pair's first token: the same launch on the two prefills' logits
+            other, Sn = free[1], neg_ids.shape[1]
+            self.cache.key_valid[other] = 1
+            out_u = self.model(input_ids=neg_ids, images=negative_images, attention_mask=neg_mask,
+                               past_key_values=type(self.cache).rows_of(self.cache, other, other + 1), use_cache=True)
+            both = torch.cat([last, out_u.logits[0, -1:]]).float().contiguous()
+            ops.guide(both, ops.guidance_rows(2, [(0, 1, *guide)], device=self.ll.device))
+            last = both[:1]
         scored = None
         if self.logprobs is not None:                            # the raw logits: before the processors and the draw rewrite them
             last = last.float().contiguous()
@@ -270,6 +303,18 @@ class ContinuousBatcher:
                 self.sess.sample[slot:slot + 1].copy_(params)
             self.sess.pos[slot:slot + 1].fill_(S)
             self.sess.tok[slot:slot + 1].fill_(tok)
+        if guide is not None:                                    # the pair's rows of the step's table, read at the next replay
+            self.sess.pos[other:other + 1].fill_(Sn)
+            self.sess.tok[other:other + 1].fill_(tok)
+            if self.sess.sample is not None:                     # the unconditional slot: a greedy, neutral row that follows
+                self.sess.sample[other:other + 1].copy_(ops.sampling_rows(0.0, device=self.ll.device))
+            if self.sess.proc is not None:
+                self.sess.proc[other:other + 1].copy_(ops.processor_rows([None], device=self.ll.device))
+            pair = ops.guidance_rows(self.slots, [(slot, other, *guide)], device=self.ll.device)
+            self.sess.guide[slot:slot + 1].copy_(pair[slot:slot + 1])
+            self.sess.guide[other:other + 1].copy_(pair[other:other + 1])
+            self.partner[slot], self.partner[other], self.uncond[other] = other, slot, True
+            self.live[other], self.length[other] = True, Sn
         if scored is not None:                                   # the first token sits at index S of the request's sequence
             tabs = None if not self.logprobs else tuple(t[slot:slot + 1] for t in self.sess.lp_top_tables)
             ops.score_record(*scored[:2], self.sess.tok[slot:slot + 1], self.sess.lp_table[slot:slot + 1], None, S,
@@ -289,6 +334,8 @@ class ContinuousBatcher:
         # a slot whose cache rows are full leaves the batch here (reported in self.full) instead of failing the shared
         # step of every other live request
         self.full = [i for i in range(self.slots) if self.live[i] and self.length[i] + 1 > self.ctx_max]
+        if self.guidance:                                        # a pair leaves when either slot is full, reported by its conditional slot
+            self.full = sorted({self.partner[i] if self.uncond[i] else i for i in self.full})
         for i in self.full:
             self.release(i)
         if not any(self.live):
@@ -311,6 +358,8 @@ class ContinuousBatcher:
         for i in range(self.slots):
             if self.live[i]:
                 self.length[i] += 1
+                if self.uncond[i]:                               # advances with its pair, reported by the conditional slot alone
+                    continue
                 out[i] = toks[i]
                 if rows is not None:
                     self.last_logprobs[i] = rows[i]
@@ -332,6 +381,12 @@ class ContinuousBatcher:
         if self.constraints is not None:                         # the slot's row back to neutral: nothing carries over
             self.sess.con[slot:slot + 1].copy_(ops.constraint_rows(self.constraints, 1, flags=0))
         self.live[slot] = False
+        if self.guidance and self.partner[slot] is not None:     # both slots of a pair leave, their rows back to neutral
+            other = self.partner[slot]
+            neutral = ops.guidance_rows(1, device=self.ll.device)
+            for i in (slot, other):
+                self.sess.guide[i:i + 1].copy_(neutral)
+                self.partner[i], self.uncond[i], self.live[i] = None, False, False
 
     def speculation(self, slot: int) -> dict:
         """{"steps", "drafted", "accepted"} of the request in ``slot`` (a speculating batcher; kept until the slot is reused)."""

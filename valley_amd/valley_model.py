@@ -649,7 +649,8 @@ class ValleyLlamaForCausalLM:
                  no_repeat_ngram_size=None, min_length=None, min_new_tokens=None, output_logprobs: bool = False,
                  top_logprobs: int = 0, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, prefix=None,
                  bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, forced_eos_token_id=None,
-                 allowed_sequences=None, **kw):
+                 allowed_sequences=None, guidance_scale=None, negative_prompt_ids=None, negative_prompt_attention_mask=None,
+                 negative_images=None, guidance_plausibility=0.0, **kw):
         """Prefill + per-token KV decode (the loop of serve/model_worker.py:371-394; the reference's CLI
         path reaches the same through HF ``generate``, valley_model.py:432).  Greedy when not sampling or
         temperature < 1e-4, else temperature softmax + multinomial.  Decode steps run through a
@@ -684,6 +685,19 @@ class ValleyLlamaForCausalLM:
         changes and nothing more is launched.  (``prefix_allowed_tokens_fn`` itself, ``sequence_bias`` and grammars are not
         provided.)
 
+        ``guidance_scale`` / ``negative_prompt_ids`` / ``negative_prompt_attention_mask`` are HF's classifier-free guidance
+        (UnbatchedClassifierFreeGuidanceLogitsProcessor, the first processor of HF's list): every prompt is decoded in two rows
+        of one captured step, its own and an unconditional one behind the negative prompt (None: the prompt's last token, as
+        in HF), and the next-token scores are scale * (lc - lu) + lu over the two rows' log-softmaxes, combined on the device
+        (ops.guide) in front of the processors, the constraints and the draw.  ``negative_images`` are the frames of the
+        unconditional row (None: text only) — visual contrastive decoding is ``negative_prompt_ids=input_ids`` with noised
+        frames, or without any.  ``guidance_plausibility`` = beta in [0, 1] keeps only the tokens whose conditional probability
+        reaches beta times the most probable one's (contrastive decoding's plausibility constraint; 0 = off, HF).  A scale of
+        None or 1 is off: that call launches what it launched before.  Greedy and sampling, the processors and the token
+        constraints (they see the conditional ``input_ids``), a left-padded batch, ``use_graph`` True or False, the bf16, fp16,
+        int8 and int4 engines; at most 4 prompt rows, no beams, no ``prompt_lookup_num_tokens``, no ``prefix=``, no
+        ``output_logprobs``, no fp32 engine, no ``use_graph=None`` — refused before a launch.
+
         ``output_logprobs`` (with ``return_dict_in_generate``): the result gains ``token_logprobs`` fp32 [B, new tokens] =
         log_softmax(raw model logits)[token] — before the processors, the temperature and top-k / top-p; HF's
         ``compute_transition_scores(sequences, out.logits, normalize_logits=True)`` — and, with ``top_logprobs = n`` in
@@ -710,6 +724,9 @@ class ValleyLlamaForCausalLM:
         beams, no padding mask, a 16-bit engine — anything else is refused before a launch.  Everything else the one-row call
         takes (sampling, the processors, ``output_logprobs``, ``prompt_lookup_num_tokens``, every ``use_graph``, the int8 and
         int4 engines) works unchanged: the loops below are the same, only their cache and first forward come from the session."""
+        guide = generation.guidance_args(self, input_ids, guidance_scale, negative_prompt_ids, negative_prompt_attention_mask,
+                                         negative_images, guidance_plausibility, num_beams, prompt_lookup_num_tokens, prefix,
+                                         output_logprobs or top_logprobs, use_graph)      # None: off (a scale of None or 1)
         if prefix is not None:
             if num_beams is not None and not isinstance(num_beams, bool) and int(num_beams) > 1:
                 raise ValueError("prefix= is not supported with num_beams > 1 (the beams' rows are not a session's one row)")
@@ -752,6 +769,11 @@ class ValleyLlamaForCausalLM:
                                                          use_graph=bool(use_graph), spec=spec, do_sample=do_sample, temperature=temperature,
                                                          top_k=top_k, top_p=top_p, prefix=prefix)
             return SimpleNamespace(sequences=seq, sequences_scores=None, speculation=speculation) if return_dict_in_generate else seq
+        if guide is not None:
+            seq = generation._generate_guided(self, input_ids, images, attention_mask, max_new_tokens, do_sample, temperature,
+                                              stopping_criteria, eos_token_id, use_graph, top_k, top_p, seed,
+                                              kw.get("pad_token_id", getattr(self.config, "pad_token_id", None)), guide, proc=proc, con=con)
+            return SimpleNamespace(sequences=seq, sequences_scores=None) if return_dict_in_generate else seq
         seq, lp_out = generation._generate(self, input_ids, images, attention_mask, max_new_tokens, do_sample, temperature, stopping_criteria,
                                            eos_token_id, use_graph, top_k, top_p, seed,
                                            kw.get("pad_token_id", getattr(self.config, "pad_token_id", None)), proc=proc,
@@ -886,7 +908,7 @@ class ValleyLlamaForCausalLM:
                                                             "output_logprobs", "top_logprobs", "prompt_lookup_num_tokens",
                                                             "max_matching_ngram_size", "seed", "prefix", "bad_words_ids",
                                                             "suppress_tokens", "begin_suppress_tokens", "forced_eos_token_id",
-                                                            "allowed_sequences")}
+                                                            "allowed_sequences", *generation.GUIDANCE_KEYS)}
         self.last_generation = None
         if gk.get("output_logprobs"):                        # the log-probabilities of the answer: kept on ``last_generation``
             self.last_generation = self.generate(input_ids=input_ids, images=images, stopping_criteria=[stopping],
