@@ -32,6 +32,7 @@ LIB_SPEC_ROWS = os.path.join(LIBDIR, "libvalley_hip_spec_rows.so")         # the
 LIB_SUFFIX = os.path.join(LIBDIR, "libvalley_hip_suffix.so")               # split attention of 1..64 new queries over a cached prefix
 LIB_CONSTRAIN = os.path.join(LIBDIR, "libvalley_hip_constrain.so")         # token constraints: bad words, suppressed ids, forced EOS, tries
 LIB_GUIDE = os.path.join(LIBDIR, "libvalley_hip_guide.so")                 # classifier-free guidance: the two rows' combine, the token follow
+LIB_STOP = os.path.join(LIBDIR, "libvalley_hip_stop.so")                   # the end of a generation: EOS, HF's stop strings, the pad rule
 # the C prologue every companion compiles (error text, launch check, the version / last-error entry points)
 COMPANION_SHARED = ["companion_capi.hpp"]
 
@@ -77,6 +78,11 @@ COMPANIONS_GUIDE = (
     Companion("guide", LIB_GUIDE, ("guide.hip",), "valley_hip_guide.h", ("beam_rows.inc",)),
 )
 EVERY_COMPANION = (*ALL_COMPANIONS, *COMPANIONS_GUIDE)
+# stop strings on the device: a sixth table.  EVERY_COMPANION is what the guidance tests count, so it keeps its five tables and
+# the build walks (*EVERY_COMPANION, *COMPANIONS_STOP)
+COMPANIONS_STOP = (
+    Companion("stop", LIB_STOP, ("stop.hip",), "valley_hip_stop.h", ()),
+)
 SOURCES = ["capi.hip", "gemm_bf16.hip", "gemm_p32.hip", "gemm_p16.hip", "gemm_streamk.hip", "norm_elementwise.hip", "attention.hip", "temporal_delta.hip", "preprocess.hip", "gemv_bf16.hip", "precise_f32.hip", "gemm_skinny.hip", "decode_step.hip", "sampling.hip"]
 
 
@@ -92,8 +98,8 @@ def hipcc() -> str:
 
 def needs_build() -> bool:
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h)
-                                                                 for h in ("valley_hip.h", *(c.header for c in EVERY_COMPANION))]
-    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, *(c.lib for c in EVERY_COMPANION)):
+                                                                 for h in ("valley_hip.h", *(c.header for c in (*EVERY_COMPANION, *COMPANIONS_STOP)))]
+    for lib in (LIB, LIB_F16, LIB_EXP, LIB_EXP_F16, *(c.lib for c in (*EVERY_COMPANION, *COMPANIONS_STOP))):
         if not os.path.exists(lib):
             return True
         t = os.path.getmtime(lib)
@@ -105,7 +111,7 @@ def needs_build() -> bool:
 def build(force: bool = False, verbose: bool = True) -> str:
     """The two shipped libraries (bf16 and fp16 storage) and the experimental one, every stale translation unit compiled in parallel."""
     os.makedirs(LIBDIR, exist_ok=True)
-    for sub in ("f16", "exp", "exp_f16", *(c.name for c in EVERY_COMPANION)):
+    for sub in ("f16", "exp", "exp_f16", *(c.name for c in (*EVERY_COMPANION, *COMPANIONS_STOP))):
         os.makedirs(os.path.join(LIBDIR, sub), exist_ok=True)
     if not force and not needs_build():
         return LIB
@@ -134,7 +140,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
             jobs.append((s, cmd))
             if s in AUDITED:
                 audits.append((s, odir, " ".join(flags) or "(default flags)"))
-    for c in EVERY_COMPANION:
+    for c in (*EVERY_COMPANION, *COMPANIONS_STOP):
         cdir = os.path.join(LIBDIR, c.name)
         for s in c.sources:
             o = os.path.join(cdir, s.replace(".hip", ".o"))
@@ -184,7 +190,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
-    for c in EVERY_COMPANION:
+    for c in (*EVERY_COMPANION, *COMPANIONS_STOP):
         cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", c.lib] + \
             [os.path.join(LIBDIR, c.name, s.replace(".hip", ".o")) for s in c.sources]
         if verbose:

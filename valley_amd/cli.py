@@ -133,9 +133,21 @@ def main(args) -> str:
     # HF's prompt_lookup_num_tokens: same answer, fewer decode steps (sampled: the same answer as the same seed without it)
     gen.update(lookup_kwargs(getattr(args, "prompt_lookup", None), getattr(args, "seed", None), sampled))
     gen.update(guidance_kwargs(tokenizer, getattr(args, "guidance_scale", None), getattr(args, "negative_prompt", None)))
+    gen.update(stop_kwargs(getattr(args, "stop_on_device", False), getattr(args, "sync_every", None)))
     answer = model.completion(tokenizer, args.video_file, turns, gen, _require_gpu())
     print(answer)
     return answer
+
+
+def stop_kwargs(stop_on_device: bool = False, sync_every: Optional[int] = None) -> dict:
+    """The ``completion`` keys of ``--stop-on-device`` / ``--sync-every N``: nothing without the flag.  The separator '###' is
+    then HF's stop string, tested on the device over the answer, instead of the reference's host callback; with N > 1 the
+    host looks at the generation once per N tokens."""
+    if not stop_on_device:
+        if sync_every is not None:
+            raise ValueError("--sync-every needs --stop-on-device")
+        return {}
+    return {"stop_strings": ["###"], **({} if sync_every is None else {"sync_every": int(sync_every)})}
 
 
 def guidance_kwargs(tokenizer, guidance_scale=None, negative_prompt=None) -> dict:
@@ -175,7 +187,15 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
                          "away from it by G (1 = off)")
     ap.add_argument("--negative-prompt", type=str, default=None, metavar="TEXT",
                     help="the unconditional row's prompt, as text without frames (default: the prompt's last token, as in HF)")
-    return ap.parse_args(argv)
+    ap.add_argument("--stop-on-device", action="store_true",
+                    help="test the separator '###' on the device, inside the decode step (HF's stop_strings), instead of decoding "
+                         "the answer on the host after every token")
+    ap.add_argument("--sync-every", type=int, default=None, metavar="N",
+                    help="with --stop-on-device: run N decode steps between two looks at the generation (the answer is the same)")
+    args = ap.parse_args(argv)
+    if args.sync_every is not None and not args.stop_on_device:
+        ap.error("--sync-every needs --stop-on-device")
+    return args
 
 
 # ---- valley/inference/run_valley_llamma_v2.py ------------------------------------------------------------------------

@@ -69,7 +69,7 @@ class DecodeSession:
     def __init__(self, llama: HipLlama, cache: HipKVCache, use_graph: bool = True, per_row_positions: bool = False,
                  sampling: bool = False, beams: Optional[tuple] = None, processors: bool = False,
                  processor_eos: Optional[Sequence[int]] = None, logprobs: Optional[int] = None, constraints=None,
-                 guidance: bool = False):
+                 guidance: bool = False, stop=None, stop_eos: Optional[Sequence[int]] = None):
         """``per_row_positions``: every batch row is an independent sequence at its own position (``pos`` is int32 [B]
         and advances by one per step for every row) — the captured step of valley_amd.serving.ContinuousBatcher.
         ``sampling``: the step draws each row's next token with that row's parameters in ``self.sample`` (int32 [B, 6],
@@ -106,7 +106,17 @@ class DecodeSession:
         written, read at every replay).  Right behind the lm_head a conditional row's logits are combined with its
         unconditional partner's (ops.guide: HF puts this processor first), then the processors, the constraints and the
         argmax / draw run as ever, and the unconditional row takes its conditional row's token (ops.guide_follow) before
-        pos += 1: both rows of a pair are fed the same token at the next step."""
+        pos += 1: both rows of a pair are fed the same token at the next step.
+        ``stop`` (an ops.StopTables; not with beams or guidance): the end of a row's generation is decided inside the step, right
+        behind the argmax / draw (ops.stop): a watched row finishes when the chosen token is one of ``stop_eos`` or HF's
+        stop-string test fires on the row's last tokens in ``self.hist`` followed by it, and a finished row's tokens become its
+        pad id.  Each row's flags, first matchable index and pad id are in ``self.stop_rows`` (int32 [B, 4], ops.stop_rows; no row
+        is watched until written), the verdicts in ``self.stop_state`` (int32 [B, 2] = {finished, index of the finishing token};
+        the caller clears a row with ops.stop_state's values).  It implies ``processors`` (that launch appends the fed token to the
+        history; its rows stay neutral unless written).  Rows, state, tables and EOS ids are read at every replay, so the host
+        may replay several steps and read ``self.stop_state`` once."""
+        if stop is not None and (beams is not None or guidance):
+            raise ValueError("DecodeSession(stop=) takes no beams and no guidance")
         self.ll, self.cache = llama, cache
         B, d = cache.batch, llama.device
         if B > 8:
@@ -173,6 +183,13 @@ class DecodeSession:
             if beams is not None or logprobs is not None:
                 raise ValueError("DecodeSession(guidance=True) takes no beams and no logprobs")
             self.guide = ops.guidance_rows(B, device=d)
+        self.stop_tables, self.stop_rows, self.stop_state, self.stop_eos = stop, None, None, None
+        if stop is not None:
+            processors = True
+            self.stop_rows = ops.stop_rows(B, watch=False, device=d)
+            self.stop_state = ops.stop_state(B, device=d)
+            if stop_eos:
+                self.stop_eos = torch.tensor([int(e) for e in stop_eos], dtype=torch.int32, device=d)
         self.proc = self.hist = self.proc_eos = None
         self.con, self.con_tables = None, constraints
         if constraints is not None:
@@ -269,6 +286,8 @@ class DecodeSession:
             ops.argmax(self.logits[:, :ll.V], sampling=self.sample, ctr=self.pos, ctr_add=1, out=self.tok)
         if self.lp_n is not None:                    # the token just chosen has index pos + 1 in its row's sequence
             self._record(1)
+        if self.stop_tables is not None:             # the history holds the row up to the fed token, index pos; tok is index pos + 1
+            ops.stop(self.tok, self.stop_rows, self.stop_state, self.stop_tables, self.hist, self.pos, 0, eos=self.stop_eos)
         if self.guide is not None:                   # the unconditional row is fed its conditional row's token
             ops.guide_follow(self.tok, self.guide)
         ops.incr_i32(self.pos, 1)
@@ -344,6 +363,7 @@ class DecodeSession:
         pos0, tok0 = self.pos.clone(), self.tok.clone()
         beam0 = None
         hist0 = None if self.hist is None else self.hist.clone()   # the warm-up step appends / gathers: restored
+        stop0 = None if self.stop_state is None else self.stop_state.clone()   # ... and may finish a row: restored
         lp0 = None
         if self.lp_n is not None:                            # the warm-up step records a column: restored
             lp0 = [(t, t.clone()) for t in [self.lp_table] + list(self.lp_top_tables or ())]
@@ -359,6 +379,8 @@ class DecodeSession:
         self.tok.copy_(tok0)
         if hist0 is not None:
             self.hist.copy_(hist0)
+        if stop0 is not None:
+            self.stop_state.copy_(stop0)
         for t, t0 in lp0 or ():
             t.copy_(t0)
         if beam0 is not None:

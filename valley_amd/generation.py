@@ -209,6 +209,65 @@ def token_loop(step, token, seq, finished, eos, stopping_criteria, max_new_token
     return seq
 
 
+STOP_KEYS = ("stop_strings", "stop_begin", "sync_every")
+NO_TOKENIZER = ("There are one or more stop strings, either in the arguments to `generate` or in the model's generation config, but "
+                "we could not locate a tokenizer. When generating with stop strings, you must pass the model's tokenizer to the "
+                "`tokenizer` argument of `generate`.")                       # HF's message
+
+
+def stop_args(model, input_ids, stop_strings, tokenizer, stop_begin, sync_every, num_beams, prompt_lookup_num_tokens, guided,
+              stopping_criteria, do_sample, temperature, top_k, top_p, seed, output_logprobs, use_graph, eos_token_id):
+    """``generate``'s stop arguments checked -> (ops.StopTables on the host, stop_begin, sync_every), or None where the end of the
+    generation stays with the host (no ``stop_strings``, ``sync_every`` 1): that call launches what it launched before.  Every
+    combination the loops do not cover is refused here, before the model is touched; the tables are built on the host."""
+    if isinstance(sync_every, bool) or not isinstance(sync_every, int) or sync_every < 1:
+        raise ValueError(f"sync_every must be an int >= 1, got {sync_every!r}")
+    if stop_strings is None and sync_every == 1:
+        return None
+    if stop_begin not in ("sequence", "generated"):
+        raise ValueError(f'stop_begin must be "sequence" or "generated", got {stop_begin!r}')
+    what = "stop_strings" if stop_strings is not None else "sync_every > 1"
+    if num_beams is not None and not isinstance(num_beams, bool) and int(num_beams) > 1:
+        raise ValueError(f"{what} is not supported with num_beams > 1")
+    if prompt_lookup_num_tokens is not None:
+        raise ValueError(f"{what} is not supported with prompt_lookup_num_tokens")
+    if guided:
+        raise ValueError(f"{what} is not supported with guidance_scale")
+    if sync_every > 1:
+        if stopping_criteria:
+            raise ValueError("sync_every > 1 is not supported with stopping_criteria (a host callback looks at every token)")
+        if do_sample and temperature >= ops.GREEDY_T and top_k is None and top_p is None and seed is None:
+            raise ValueError("sync_every > 1 is not supported with do_sample without top_k / top_p / seed (the host draws every token)")
+        if output_logprobs:
+            raise ValueError("sync_every > 1 is not supported with output_logprobs")
+        if use_graph is None or input_ids.shape[0] > 8 or model.model.precision == "fp32":
+            raise ValueError("sync_every > 1 needs the decode session: use_graph True (captured) or False (eager), not None, at "
+                             "most 8 rows, not the fp32 engine")
+        if stop_strings is None and not eos_ids(eos_token_id):
+            raise ValueError("sync_every > 1 needs stop_strings or an eos_token_id (nothing on the device would end the generation)")
+    if stop_strings is not None and tokenizer is None:
+        raise ValueError(NO_TOKENIZER)
+    return ops.stop_tables(tokenizer, () if stop_strings is None else stop_strings), stop_begin, sync_every
+
+
+def block_loop(sess, S, max_new_tokens, sync_every, cache):
+    """The loop of ``_generate`` behind the first token where the device decides the end (DecodeSession ``stop``): up to
+    ``sync_every`` steps are enqueued, then ``sess.stop_state`` is read — the block's only device-to-host traffic — until every
+    row has finished, at ``max_new_tokens`` or with the cache full.  -> the new tokens [B, n] (one read of the history and the
+    last chosen token), cut at the step where the last row finished: steps replayed behind the end are dropped."""
+    steps = 0
+    while True:
+        state = sess.stop_state.cpu()
+        left = min(max_new_tokens - 1 - steps, cache.ctx_max - cache.seq_len)
+        if bool(state[:, 0].all()) or left <= 0:
+            break
+        for _ in range(min(sync_every, left)):
+            sess.step()
+        steps += min(sync_every, left)
+    new = torch.cat([sess.hist[:, S:S + steps], sess.tok[:, None]], dim=1).to(torch.long)
+    return new[:, :int(state[:, 1].max()) + 1 - S] if bool(state[:, 0].all()) else new
+
+
 def sampling_setup(do_sample, temperature, top_k, top_p, seed, B, device):
     """(greedy, per-row parameters of the on-device draw or None): sampling with any of top_k / top_p / seed draws on the device,
     row r with seed + r (or its own seed of a list); without a seed one is drawn from torch's generator."""
@@ -225,9 +284,12 @@ def sampling_setup(do_sample, temperature, top_k, top_p, seed, B, device):
 
 
 def _generate(model, input_ids, images, attention_mask, max_new_tokens, do_sample, temperature, stopping_criteria, eos_token_id,
-              use_graph, top_k, top_p, seed, pad, proc=None, logprobs=None, prefix=None, con=None):
+              use_graph, top_k, top_p, seed, pad, proc=None, logprobs=None, prefix=None, con=None, stop=None):
     """Greedy decoding and sampling: the first token from the prefill's logits, then one ``step`` per token (the decode session's, or
-    the generic forward's) until every row has finished; a finished row emits ``pad`` (HF).  -> sequences, log-probability fields."""
+    the generic forward's) until every row has finished; a finished row emits ``pad`` (HF).  -> sequences, log-probability fields.
+    ``stop`` (stop_args'): EOS and HF's stop strings are tested on the device behind every chosen token (ops.stop: inside the
+    session's step, eagerly behind the first token, the generic forward's and a host draw), and with ``sync_every`` > 1 the
+    session's steps run in blocks (``block_loop``)."""
     d = model.device
     input_ids = input_ids.to(d)
     B, S = input_ids.shape
@@ -250,6 +312,15 @@ def _generate(model, input_ids, images, attention_mask, max_new_tokens, do_sampl
     if con is not None and table is None:                    # the constraints read the history the processors' launch appends to
         table = ops.processor_rows([None] * B, device=d)
     rewritten = table is not None or sample is not None      # the logits are rewritten in place before the token is picked
+    if stop is not None and table is None:                   # the stop test reads that history too (neutral rows rewrite nothing)
+        table = ops.processor_rows([None] * B, device=d)
+    eos32 = None if eos is None or table is None else eos.to(torch.int32)
+    st_rows = st_state = st_tables = None
+    sync_every = 1
+    if stop is not None:                                     # every row watched; a finished row's tokens become pad
+        st_tables, sync_every = stop[0]._replace(buf=stop[0].buf.to(d)), stop[2]
+        st_rows = ops.stop_rows(B, begin=S if stop[1] == "generated" else 0, pad=pad, pad_after=True, device=d)
+        st_state = ops.stop_state(B, device=d)
     lp_cols, lp_done = [], []                                # per new token: its [B, 1(, n)] record; the rows already finished
 
     def record(scored, tok):
@@ -262,9 +333,8 @@ def _generate(model, input_ids, images, attention_mask, max_new_tokens, do_sampl
 
     last = out.logits[:, -1, :].contiguous()
     scored = score_raw(last, logprobs, rewritten) if logprobs is not None else None
-    eos32 = hist = None
+    hist = None
     if table is not None:                                    # HF's processors over each row's whole input_ids, on the device
-        eos32 = None if eos is None else eos.to(torch.int32)
         hist = torch.zeros((B, cache.ctx_max), dtype=torch.int32, device=d)
         hist[:, :S] = input_ids.to(torch.int32)
         ops.logits_process(last, table, hist, None, S, None, eos32)
@@ -273,6 +343,8 @@ def _generate(model, input_ids, images, attention_mask, max_new_tokens, do_sampl
     token = pick(last, S)
     if logprobs is not None:                                 # the first token: from the prefill's last logits
         record(scored, token)
+    if stop is not None:                                     # the same launch over the prompt's history: the token has index S
+        ops.stop(token.to(torch.int32), st_rows, st_state, st_tables, hist, None, S - 1, eos=eos32)
     seq = torch.cat([input_ids, token[:, None]], dim=1)
     if B > 8 or model.model.precision == "fp32":
         use_graph = None                                     # the GEMV decode session is bf16, for <= 8 sequences
@@ -281,13 +353,18 @@ def _generate(model, input_ids, images, attention_mask, max_new_tokens, do_sampl
         from .decode import DecodeSession
         sess = DecodeSession(model.model.llama, cache, use_graph=bool(use_graph), sampling=sample is not None, processors=table is not None,
                              processor_eos=eos_list, **({} if logprobs is None else {"logprobs": logprobs}),
-                             **({} if con is None else {"constraints": con[0]}))
+                             **({} if con is None else {"constraints": con[0]}),
+                             **({} if stop is None or not on_device else {"stop": st_tables, "stop_eos": eos_list}))
         if sample is not None:
             sess.sample.copy_(sample)
         if table is not None:
             sess.proc.copy_(table)
         if con is not None:
             sess.con.copy_(con[1])
+        if stop is not None and on_device:                   # the step tests the token it chose; the state goes on from the first
+            sess.stop_rows.copy_(st_rows)
+            sess.stop_state.copy_(st_state)
+            st_state = sess.stop_state
         sess.begin(token, prompt_ids=input_ids if table is not None else None)
 
     def session_step(token):
@@ -298,6 +375,8 @@ def _generate(model, input_ids, images, attention_mask, max_new_tokens, do_sampl
             sess.tok.copy_(token.to(torch.int32))
             if logprobs is not None and not on_device:
                 sess.record_token()                          # the step recorded its own argmax: the host's draw replaces it
+        if stop is not None and not on_device:               # the host's draw is tested (pos has advanced: the history ends at pos - 1)
+            ops.stop(sess.tok, st_rows, st_state, st_tables, sess.hist, sess.pos, -1, eos=eos32)
         if logprobs is not None:
             lp_done.append(finished.clone())
         return token
@@ -315,10 +394,17 @@ def _generate(model, input_ids, images, attention_mask, max_new_tokens, do_sampl
         token = torch.where(finished, torch.full_like(token, pad), pick(last, cache.seq_len))
         if logprobs is not None:
             record(scored, token)
+        if stop is not None:                                 # the history ends at the fed token, index seq_len - 1
+            ops.stop(token.to(torch.int32), st_rows, st_state, st_tables, hist, None, cache.seq_len - 1, eos=eos32)
         return token
 
-    step = forward_step if sess is None else session_step
-    seq = token_loop(step, token, seq, finished, eos, stopping_criteria, max_new_tokens, cache, d)
+    if sync_every > 1:                                       # the device decides the end and pads; the host looks once per block
+        seq = torch.cat([input_ids, block_loop(sess, S, max_new_tokens, sync_every, cache).to(input_ids.dtype)], dim=1)
+    else:
+        if stop is not None:                                 # the device's verdict joins the criteria: no token leaves the device for it
+            stopping_criteria = [*(stopping_criteria or ()), lambda seqs, scores: st_state[:, 0] != 0]
+        step = forward_step if sess is None else session_step
+        seq = token_loop(step, token, seq, finished, eos, stopping_criteria, max_new_tokens, cache, d)
     finish(d, sess)
     lp_out = {}
     if logprobs is not None:                                 # one read of the session's tables, after the loop

@@ -1813,6 +1813,123 @@ def guide_follow(tok: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
     return tok
 
 
+# ---- the end of a generation on the device (libvalley_hip_stop.so, include/valley_hip_stop.h) -------------------------------
+# the header's limits and flag bits: their one Python home (the binding module is imported only by a launch).
+# STOP_MAX_WIDTH bounds what the kernel accepts as a table row; 8 strings of 64 characters reach 8 * (63 + 64) + 1 = 1017 ints,
+# so no input the other limits allow exceeds it: the packer's check guards the limits against being raised one without the other
+STOP_MAX_STRINGS, STOP_MAX_LEN, STOP_MAX_WIDTH, STOP_HEADER = 8, 64, 1024, 16      # VLY_STOP_<limit>
+STOP_WATCH, STOP_PAD_AFTER = 1, 2                                                   # VLY_STOP_<flag>
+
+
+class StopTables(NamedTuple):
+    """HF's StopStringCriteria tables as ``stop`` reads them: ``buf`` int32 [STOP_HEADER + T * W] = the header
+    {n strings, max_valid_positions, max_valid_end_lens, maximum_token_len, T, W, 0, 0, target_lens[8]} and embedding_vec."""
+    buf: torch.Tensor
+    strings: tuple
+    maximum_token_len: int
+
+
+def stop_tables(tokenizer, stop_strings, device=None) -> StopTables:
+    """The tables of HF's ``generate(stop_strings=, tokenizer=)``: a transformers ``StopStringCriteria`` is built on the host
+    (its vocabulary cleaning, the byte-fallback and byte-level modes included) and its ``embedding_vec``,
+    ``max_valid_positions``, ``max_valid_end_lens``, ``target_lens`` and ``maximum_token_len`` are packed for the device.
+    ``stop_strings``: a string or a list of at most 8 non-empty strings of at most 64 characters (bytes in the byte modes);
+    an empty list gives the empty table of a session that stops on EOS ids alone (no tokenizer needed)."""
+    strings = (stop_strings,) if isinstance(stop_strings, str) else tuple(stop_strings or ())
+    if any(not isinstance(s, str) for s in strings):
+        raise ValueError(f"stop_strings must be a string or a list of strings, got {stop_strings!r}")
+    if len(strings) > STOP_MAX_STRINGS:
+        raise ValueError(f"stop_strings: at most {STOP_MAX_STRINGS} stop strings, got {len(strings)}")
+    if any(len(s) == 0 for s in strings):
+        raise ValueError("stop_strings: an empty stop string matches everywhere")
+    if any(len(s) > STOP_MAX_LEN for s in strings):
+        raise ValueError(f"stop_strings: a stop string holds at most {STOP_MAX_LEN} characters, got {max(len(s) for s in strings)}")
+    head = torch.zeros((STOP_HEADER,), dtype=torch.int32)
+    if not strings:
+        buf = head
+        mtl = 0
+    else:
+        from transformers.generation.stopping_criteria import StopStringCriteria
+        crit = StopStringCriteria(tokenizer, list(strings))
+        emb = crit.embedding_vec.to("cpu", torch.int32).contiguous()
+        T, W = emb.shape
+        ns, mvp, mvel, mtl = len(strings), int(crit.max_valid_positions), int(crit.max_valid_end_lens), int(crit.maximum_token_len)
+        if mtl > STOP_MAX_LEN:
+            raise ValueError(f"stop_strings: a stop string holds at most {STOP_MAX_LEN} bytes, got {mtl}")
+        if W > STOP_MAX_WIDTH:
+            raise ValueError(f"stop_strings: a table row of {W} ints (the strings' valid positions and end overlaps per token) "
+                             f"exceeds {STOP_MAX_WIDTH}")
+        assert W == ns * (mvp + mvel) + 1, (W, ns, mvp, mvel)
+        head[:6] = torch.tensor([ns, mvp, mvel, mtl, T, W], dtype=torch.int32)
+        head[8:8 + ns] = crit.target_lens.to("cpu", torch.int32)
+        buf = torch.cat([head, emb.view(-1)])
+    return StopTables(buf.to(device) if device is not None else buf, strings, mtl)
+
+
+def stop_rows(R: int, begin=0, pad=0, watch=True, pad_after=False, device=None) -> torch.Tensor:
+    """Per-row parameters of ``stop`` as int32 [R, 4]: {flags, begin, pad id, 0}.  ``begin``: the first index of the row's
+    sequence the stop strings may match in (0: HF, the prompt's last tokens count; the prompt's length: only generated text).
+    ``watch``: the row is tested at all; ``pad_after``: once finished, its chosen tokens become ``pad``.  Scalars or one value
+    per row."""
+    if isinstance(R, bool) or not isinstance(R, int) or R < 1:
+        raise ValueError(f"stop_rows: R must be an int >= 1, got {R!r}")
+
+    def col(v, name):
+        v = v.reshape(-1).tolist() if isinstance(v, torch.Tensor) else v
+        v = list(v) if isinstance(v, (list, tuple)) else [v] * R
+        if len(v) != R or any(not isinstance(a, int) for a in v):
+            raise ValueError(f"stop_rows: {name} must be an int or {R} ints, got {v}")
+        return [int(a) for a in v]
+    b, p, w, a = col(begin, "begin"), col(pad, "pad"), col(watch, "watch"), col(pad_after, "pad_after")
+    if any(x < 0 for x in b):
+        raise ValueError(f"stop_rows: begin >= 0 expected, got {b}")
+    f = [(STOP_WATCH if w[r] else 0) | (STOP_PAD_AFTER if a[r] else 0) for r in range(R)]
+    out = torch.tensor([f, b, p, [0] * R], dtype=torch.int32).t().contiguous()
+    return out.to(device) if device is not None else out
+
+
+def stop_state(R: int, device=None) -> torch.Tensor:
+    """The cleared state of ``stop``, int32 [R, 2] = {finished, end}: nobody has finished, every end is -1."""
+    if isinstance(R, bool) or not isinstance(R, int) or R < 1:
+        raise ValueError(f"stop_state: R must be an int >= 1, got {R!r}")
+    out = torch.tensor([[0, -1]] * R, dtype=torch.int32)
+    return out.to(device) if device is not None else out
+
+
+def stop(tok: torch.Tensor, rows: torch.Tensor, state: torch.Tensor, tables: StopTables, hist: torch.Tensor,
+         pos_dev: Optional[torch.Tensor] = None, pos_add: int = 0, eos: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Behind the argmax / draw over tok int32 [R]: a watched row of ``rows`` (int32 [R, 4], ``stop_rows``) finishes —
+    ``state`` (int32 [R, 2], ``stop_state``) becomes {1, index of tok[r] in the row's sequence} — when tok[r] is one of ``eos``
+    (int32 [n] on the device) or HF's stop-string test of ``tables`` fires on the row's last tokens: the history ``hist``
+    (int32 [R, L]) up to index ``pos_dev[r]`` (int32 [R]) or ``pos_dev[0]`` (int32 [1]) plus ``pos_add``, then tok[r].  A row
+    that had finished before gets its pad id into tok[r] if its rows ask for it.  Everything is read on the device."""
+    from . import lib_stop
+    _chk(tok, torch.int32, "tok")
+    _chk(rows, torch.int32, "rows")
+    _chk(state, torch.int32, "state")
+    _chk(hist, torch.int32, "hist")
+    _chk(tables.buf, torch.int32, "tables")
+    R = tok.numel()
+    if tok.dim() != 1 or tuple(rows.shape) != (R, 4) or tuple(state.shape) != (R, 2) or hist.dim() != 2 or hist.shape[0] != R:
+        raise ValueError(f"stop: tok [R], rows [R, 4], state [R, 2] and hist [R, L] expected, got {tuple(tok.shape)} / "
+                         f"{tuple(rows.shape)} / {tuple(state.shape)} / {tuple(hist.shape)}")
+    pptr, per_row = None, 0
+    if pos_dev is not None:
+        _chk(pos_dev, torch.int32, "pos_dev")
+        if pos_dev.numel() not in (1, R):
+            raise ValueError(f"stop: pos_dev must hold 1 or {R} values, got {pos_dev.numel()}")
+        pptr, per_row = pos_dev.data_ptr(), int(pos_dev.numel() == R and R > 1)
+    n_eos = 0
+    if eos is not None:
+        _chk(eos, torch.int32, "eos")
+        n_eos = eos.numel()
+    rc = lib_stop.load().vly_stop_apply(tok.data_ptr(), hist.data_ptr(), hist.shape[1], pptr, per_row, int(pos_add), rows.data_ptr(),
+                                        state.data_ptr(), tables.buf.data_ptr(), tables.buf.numel(), _ptr(eos) if n_eos else None,
+                                        n_eos, R, _stream())
+    lib_stop.check(rc, "vly_stop_apply")
+    return tok
+
+
 # ---- token log-probabilities and the forward-only loss (libvalley_hip_score.so, include/valley_hip_score.h) ----------------
 SCORE_MAX_TOP = 20       # VLY_SCORE_MAX_TOP
 SCORE_MAX_V = 1 << 18

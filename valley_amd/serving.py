@@ -17,7 +17,7 @@ import torch
 
 from . import ops
 from .decode import DecodeSession
-from .generation import eos_ids, guidance_scalars, lookup_args, negative_prompt, score_raw
+from .generation import NO_TOKENIZER, eos_ids, guidance_scalars, lookup_args, negative_prompt, score_raw
 from .valley_model import (DEFAULT_IM_END_TOKEN, DEFAULT_IM_START_TOKEN, DEFAULT_IMAGE_PATCH_TOKEN, DEFAULT_VI_END_TOKEN,
                            DEFAULT_VI_START_TOKEN, DEFAULT_VIDEO_FRAME_TOKEN, DEFAULT_VIDEO_TOKEN)
 
@@ -114,7 +114,7 @@ class ContinuousBatcher:
                  processors: bool = False, eos_token_id=None, logprobs: Optional[int] = None,
                  prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None,
                  constraints: bool = False, bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None,
-                 trie_capacity: int = 4096, guidance: bool = False):
+                 trie_capacity: int = 4096, guidance: bool = False, stop_strings=None, tokenizer=None):
         """``sampling``: the captured step draws every slot's token with the parameters ``add`` gave its request
         (temperature, top-k, top-p, seed; DecodeSession ``sampling``) — a seeded request's tokens then depend on its seed
         alone, not on its slot or its neighbours.  Greedy requests take the argmax in either kind of batcher.
@@ -143,7 +143,18 @@ class ContinuousBatcher:
         ``guidance``: the captured step runs classifier-free guidance (DecodeSession ``guidance``; ops.guide / ops.guide_follow).
         A request ``add``ed with a ``guidance_scale`` takes TWO slots — its own and an unconditional one behind its negative
         prompt — written into the step's table between steps, without a re-capture; every other request takes one, as ever.
-        Not with ``prompt_lookup_num_tokens`` or ``logprobs``."""
+        Not with ``prompt_lookup_num_tokens`` or ``logprobs``.
+        ``stop_strings`` (with ``tokenizer``; HF's names): the captured step decides for every slot whether its request is over
+        (DecodeSession ``stop``; ops.stop) — one of the strings at the end of its generated text, or one of ``eos_token_id``.
+        ``step()`` returns what it returns without them and leaves ``self.stopped`` = {slot: index of the finishing token in the
+        request's sequence} for the slots that finished since the last step (``add``'s first token included), read in the
+        step's one device-to-host copy; releasing the slot stays the caller's business.  Not with
+        ``prompt_lookup_num_tokens`` or ``guidance``."""
+        if stop_strings is not None:
+            if prompt_lookup_num_tokens is not None or guidance:
+                raise ValueError("stop_strings does not combine with prompt_lookup_num_tokens or guidance=True")
+            if tokenizer is None:
+                raise ValueError(NO_TOKENIZER)
         if not 1 <= slots <= 8:
             raise ValueError("1 <= slots <= 8 (the decode step streams weights with the GEMV kernels)")
         if guidance and (prompt_lookup_num_tokens is not None or logprobs is not None):
@@ -182,6 +193,8 @@ class ContinuousBatcher:
         if constraints:
             self.constraints = ops.constraint_tables(bad_words_ids, suppress_tokens, begin_suppress_tokens, eos=eos or None, V=self.ll.V,
                                                      capacity={"trie": int(trie_capacity), "trie_slots": slots}, device=self.ll.device)
+        self.stop = None if stop_strings is None else ops.stop_tables(tokenizer, stop_strings, device=self.ll.device)
+        self.stopped, self._told = {}, [False] * slots           # what the last step found; the slots already reported
         if self.spec_k is not None:
             self.sess = _spec.SpecRowsSession(self.ll, self.cache, self.spec_k, max_ngram=self.spec_ngram, eos_ids=eos,
                                               use_graph=use_graph, sampling=sampling)
@@ -189,7 +202,8 @@ class ContinuousBatcher:
             self.sess = DecodeSession(self.ll, self.cache, use_graph=use_graph, per_row_positions=True, sampling=sampling,
                                       processors=processors, processor_eos=eos, **({} if logprobs is None else {"logprobs": logprobs}),
                                       **({} if self.constraints is None else {"constraints": self.constraints}),
-                                      **({"guidance": True} if guidance else {}))
+                                      **({"guidance": True} if guidance else {}),
+                                      **({} if self.stop is None else {"stop": self.stop, "stop_eos": eos}))
         self.guidance = bool(guidance)
         self.partner = [None] * slots                            # a guided request's other slot, in both directions
         self.uncond = [False] * slots                            # the slot is the unconditional one of its pair
@@ -303,6 +317,14 @@ class ContinuousBatcher:
                 self.sess.sample[slot:slot + 1].copy_(params)
             self.sess.pos[slot:slot + 1].fill_(S)
             self.sess.tok[slot:slot + 1].fill_(tok)
+        if self.stop is not None:                                # the slot's row: only generated text matches, no pad rule
+            one = slice(slot, slot + 1)
+            self.sess.hist[slot, :S] = ids[0].to(torch.int32)
+            self.sess.stop_rows[one].copy_(ops.stop_rows(1, begin=S))
+            self.sess.stop_state[one].copy_(ops.stop_state(1))
+            self._told[slot] = False                             # the first token goes through the same launch
+            ops.stop(self.sess.tok[one], self.sess.stop_rows[one], self.sess.stop_state[one], self.stop, self.sess.hist[one], None,
+                     S - 1, eos=self.sess.stop_eos)
         if guide is not None:                                    # the pair's rows of the step's table, read at the next replay
             self.sess.pos[other:other + 1].fill_(Sn)
             self.sess.tok[other:other + 1].fill_(tok)
@@ -346,7 +368,14 @@ class ContinuousBatcher:
                 self.length[i] += len(toks)
             return out
         self.sess.step()
-        toks = self.sess.tok.tolist()                            # one D2H read per step for all requests
+        if self.stop is None:
+            toks = self.sess.tok.tolist()                        # one D2H read per step for all requests
+        else:                                                    # ... the slots' verdicts in the same copy
+            toks = torch.cat([self.sess.tok, self.sess.stop_state.view(-1)]).tolist()
+            state = toks[self.slots:]
+            self.stopped = {i: state[2 * i + 1] for i in range(self.slots) if self.live[i] and state[2 * i] and not self._told[i]}
+            for i in self.stopped:
+                self._told[i] = True
         rows = None
         if self.logprobs is not None:                            # ... and one more for their log-probabilities: the step's column
             # pos has advanced to the chosen token's index, at most ctx_max for a live slot: the tables' last column.  (An idle
@@ -380,6 +409,9 @@ class ContinuousBatcher:
             self.sess.release(slot)
         if self.constraints is not None:                         # the slot's row back to neutral: nothing carries over
             self.sess.con[slot:slot + 1].copy_(ops.constraint_rows(self.constraints, 1, flags=0))
+        if self.stop is not None:                                # unwatched again, nothing carries over
+            self.sess.stop_rows[slot:slot + 1].copy_(ops.stop_rows(1, watch=False))
+            self.sess.stop_state[slot:slot + 1].copy_(ops.stop_state(1))
         self.live[slot] = False
         if self.guidance and self.partner[slot] is not None:     # both slots of a pair leave, their rows back to neutral
             other = self.partner[slot]

@@ -650,7 +650,8 @@ class ValleyLlamaForCausalLM:
                  top_logprobs: int = 0, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, prefix=None,
                  bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, forced_eos_token_id=None,
                  allowed_sequences=None, guidance_scale=None, negative_prompt_ids=None, negative_prompt_attention_mask=None,
-                 negative_images=None, guidance_plausibility=0.0, **kw):
+                 negative_images=None, guidance_plausibility=0.0, stop_strings=None, tokenizer=None, stop_begin="sequence",
+                 sync_every: int = 1, **kw):
         """Prefill + per-token KV decode (the loop of serve/model_worker.py:371-394; the reference's CLI
         path reaches the same through HF ``generate``, valley_model.py:432).  Greedy when not sampling or
         temperature < 1e-4, else temperature softmax + multinomial.  Decode steps run through a
@@ -698,6 +699,19 @@ class ValleyLlamaForCausalLM:
         int8 and int4 engines; at most 4 prompt rows, no beams, no ``prompt_lookup_num_tokens``, no ``prefix=``, no
         ``output_logprobs``, no fp32 engine, no ``use_graph=None`` — refused before a launch.
 
+        ``stop_strings`` (a string or a list; needs ``tokenizer``) is HF's: a row finishes once its text ends in one of the
+        strings, wherever the token boundaries fall.  HF's StopStringCriteria builds its per-token table on the host
+        (ops.stop_tables) and the test itself runs on the device behind every chosen token (ops.stop), inside the captured
+        step too: no token leaves the device for it.  ``stop_begin="sequence"`` is HF (the prompt's last tokens count),
+        ``"generated"`` lets a match begin only behind the prompt.  The returned text is not trimmed (HF).  At most 8 strings
+        of at most 64 characters.  Greedy and sampling, the processors, the constraints, ``output_logprobs``, ``prefix=``,
+        every ``use_graph``, every engine; not with beams, ``prompt_lookup_num_tokens`` or ``guidance_scale``.
+        ``sync_every = n`` > 1: the EOS ids and the pad rule move to the device as well, the loop enqueues up to n steps and then
+        reads the rows' state once; the result is the ``sync_every=1`` result token for token (steps replayed behind the end
+        are dropped).  It needs stop strings or an ``eos_token_id``, the decode session (``use_graph`` True or False, at most 8
+        rows, not fp32) and draws on the device; not with ``stopping_criteria`` or ``output_logprobs``.  Left at their
+        defaults, nothing changes and nothing more is launched.
+
         ``output_logprobs`` (with ``return_dict_in_generate``): the result gains ``token_logprobs`` fp32 [B, new tokens] =
         log_softmax(raw model logits)[token] — before the processors, the temperature and top-k / top-p; HF's
         ``compute_transition_scores(sequences, out.logits, normalize_logits=True)`` — and, with ``top_logprobs = n`` in
@@ -727,6 +741,9 @@ class ValleyLlamaForCausalLM:
         guide = generation.guidance_args(self, input_ids, guidance_scale, negative_prompt_ids, negative_prompt_attention_mask,
                                          negative_images, guidance_plausibility, num_beams, prompt_lookup_num_tokens, prefix,
                                          output_logprobs or top_logprobs, use_graph)      # None: off (a scale of None or 1)
+        stop = generation.stop_args(self, input_ids, stop_strings, tokenizer, stop_begin, sync_every, num_beams, prompt_lookup_num_tokens,
+                                    guide is not None, stopping_criteria, do_sample, temperature, top_k, top_p, seed,
+                                    output_logprobs or top_logprobs, use_graph, eos_token_id)      # None: the host decides, as ever
         if prefix is not None:
             if num_beams is not None and not isinstance(num_beams, bool) and int(num_beams) > 1:
                 raise ValueError("prefix= is not supported with num_beams > 1 (the beams' rows are not a session's one row)")
@@ -777,7 +794,8 @@ class ValleyLlamaForCausalLM:
         seq, lp_out = generation._generate(self, input_ids, images, attention_mask, max_new_tokens, do_sample, temperature, stopping_criteria,
                                            eos_token_id, use_graph, top_k, top_p, seed,
                                            kw.get("pad_token_id", getattr(self.config, "pad_token_id", None)), proc=proc,
-                                           logprobs=top_logprobs if output_logprobs else None, prefix=prefix, con=con)
+                                           logprobs=top_logprobs if output_logprobs else None, prefix=prefix, con=con,
+                                           **({} if stop is None else {"stop": stop}))
         return SimpleNamespace(sequences=seq, sequences_scores=None, **lp_out) if return_dict_in_generate else seq
 
     def _spec_args(self, k, max_ngram, input_ids, do_sample, num_beams, rp, nr, ml, mn, logprobs, use_graph, seed=None):
@@ -891,7 +909,10 @@ class ValleyLlamaForCausalLM:
     @torch.no_grad()
     def completion(self, tokenizer, video, message: list, gen_kwargs: dict, device=None):
         """valley_model.py:424-439.  ``video`` is a path (decoded by valley_amd.video.load_video) or an
-        already preprocessed [3,T,224,224] tensor."""
+        already preprocessed [3,T,224,224] tensor.  ``gen_kwargs["stop_strings"]`` moves the end-of-answer test to the device
+        (``generate(stop_strings=)``) and replaces the keyword criterion; the strings are then matched over the answer only —
+        ``stop_begin`` is always "generated" here, a caller's value is not used — and ``sync_every`` is passed along.  Without
+        ``stop_strings`` a ``sync_every`` key is not used: the host criterion looks at every token."""
         from .video import KeywordsStoppingCriteria, load_video
         inputs = self.build_inputs(tokenizer, message)
         input_ids = torch.as_tensor(inputs.input_ids).to(self.device)
@@ -901,21 +922,26 @@ class ValleyLlamaForCausalLM:
         else:
             images = video if isinstance(video, torch.Tensor) else load_video(video)
             images = images.permute(1, 0, 2, 3).unsqueeze(0)
-        stopping = KeywordsStoppingCriteria(['###'], tokenizer, input_ids)
+        # the caller's stop strings are tested on the device, over the answer only; without them the reference's host callback
+        on_device = gen_kwargs.get("stop_strings") is not None
+        stopping = None if on_device else [KeywordsStoppingCriteria(['###'], tokenizer, input_ids)]
         gk = {k: v for k, v in gen_kwargs.items() if k in ("max_new_tokens", "do_sample", "temperature", "eos_token_id", "num_beams",
                                                             "length_penalty", "early_stopping", "repetition_penalty",
                                                             "no_repeat_ngram_size", "min_length", "min_new_tokens",
                                                             "output_logprobs", "top_logprobs", "prompt_lookup_num_tokens",
                                                             "max_matching_ngram_size", "seed", "prefix", "bad_words_ids",
                                                             "suppress_tokens", "begin_suppress_tokens", "forced_eos_token_id",
-                                                            "allowed_sequences", *generation.GUIDANCE_KEYS)}
+                                                            "allowed_sequences", *generation.GUIDANCE_KEYS) or
+              (on_device and k in ("stop_strings", "sync_every"))}
+        if on_device:
+            gk.update(tokenizer=tokenizer, stop_begin="generated")
         self.last_generation = None
         if gk.get("output_logprobs"):                        # the log-probabilities of the answer: kept on ``last_generation``
-            self.last_generation = self.generate(input_ids=input_ids, images=images, stopping_criteria=[stopping],
+            self.last_generation = self.generate(input_ids=input_ids, images=images, stopping_criteria=stopping,
                                                  return_dict_in_generate=True, **gk)
             output_ids = self.last_generation.sequences
         else:
-            output_ids = self.generate(input_ids=input_ids, images=images, stopping_criteria=[stopping], **gk)
+            output_ids = self.generate(input_ids=input_ids, images=images, stopping_criteria=stopping, **gk)
         n_in = input_ids.shape[1]
         n_diff = (input_ids != output_ids[:, :n_in]).sum().item()
         if n_diff > 0:
